@@ -8,13 +8,19 @@ per block, explicit Q, packed R and the column permutation written to HBM.  Inpu
 resident in HBM before the timed region; steps rotate over several distinct matrices so
 that the working set (207 MB per matrix) exceeds the 256 MiB Infinity Cache.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: set up, W warm-up steps, EXACTLY K timed steps, the outputs of the
+last timed step to DIR/<name>.npy if --dump-outputs is given (a fixed sample of its tiles; the inputs are seeded, so two builds can
+be compared output for output), ONE JSON line on rank 0.  --full adds every other leg to the same line: the CPU baseline, the
+comparison of the timed kernel with the oracle, steady state, host buffers, the other BASELINE configurations, and for N > 1 the
+strong-scaling legs; the --no-* switches take single legs out of a --full run.
 
 N > 1 works as typed: this process starts N ranks (torch.distributed.run, one per GPU, RCCL) BEFORE it makes any GPU call
 and exits with their return code; launched by torch.distributed.run itself (WORLD_SIZE set) it is one of the ranks.
 
 The headline `value` is weak scaling, as the path partitions: every rank factorises its own stream of 10000-block matrices
-with no data-path collective; value = all matrices of all ranks / max time.  For N > 1 the same run also measures STRONG
+with no data-path collective; value = all matrices of all ranks / max time.  For N > 1 a --full run also measures STRONG
 scaling with the only exchange the path has, reported under "strong_scaling": ONE B-block matrix cut into contiguous block
 ranges (qrkit_amd/sharding.py), every rank factorises its range, R and the permutation are gathered on rank 0 with their true
 byte counts (grouped send/recv over RCCL) INSIDE the timed region; B = 10000 (the BASELINE shape) and B = 1000000.
@@ -38,6 +44,8 @@ BLOCKS, BR, BC = 10000, 32, 32
 BYTES_PER_TILE = 8 * BR * BC + 8 * BR * BR + 8 * (BC * (BC + 1) // 2) + 4 * BC
 FLOPS_PER_TILE = (2 * BR * BC * BC - 2 * BC ** 3 / 3) + 4 * (BR * BR * BC - BR * BC * BC + BC ** 3 / 3)
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+MIN_BATCH_STEPS = 20    # a timed batch is never shorter than this (1.4 ms), unless --steps itself is
+DUMP_TILES, DUMP_SEED = 4096, 20240   # --dump-outputs: 4096 of the 10000 tiles = 52 MB as float64 (all of them would be 125 MB)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -138,7 +146,14 @@ def parse(argv):
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--warmup", type=int, default=40)
     ap.add_argument("--sets", type=int, default=8, help="distinct matrices rotated over (working set > L3)")
-    ap.add_argument("--batches", type=int, default=25, help="timed batches of exactly --steps steps each; the line reports the median batch")
+    ap.add_argument("--batches", type=int, default=25, help="the --steps timed steps are cut into at most this many batches of at least "
+                                                            f"{MIN_BATCH_STEPS} steps; the line reports the median batch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help=f"after the timed steps write Q, R and the permutation of the last timed step ({DUMP_TILES} seeded sample tiles, "
+                         "rank 0) to DIR/<name>.npy as float64")
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the headline: CPU baseline, oracle check, steady state, host "
+                                                        "buffers, other configurations, strong scaling (N > 1); the --no-* switches below take "
+                                                        "single legs out of such a run")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-check", action="store_true", help="skip the comparison of 500 tiles with the oracle (outside the timed region)")
@@ -158,9 +173,11 @@ def main():
     args = parse(argv)
     if args._cpu_worker is not None:
         return _cpu_worker(args._cpu_worker)
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # the CPU leg in the parent, before any rank (or GPU call) exists; rank 0 picks the result up from a file
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             import tempfile
             fd, path = tempfile.mkstemp(prefix="qrk_bench_cpu_", suffix=".json")
             with os.fdopen(fd, "w") as f:
@@ -182,7 +199,7 @@ def main():
 
     # the CPU leg first: this process has not touched HIP or RCCL yet (rank 0, N = 1 only)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_seconds)
     elif rank == 0 and os.environ.get("QRK_BENCH_CPU_JSON"):
         try:
@@ -249,35 +266,45 @@ def main():
 
     if args.warmup > 0:
         run(plan, args.warmup)
-    # A timed batch = EXACTLY --steps steps between barrier + synchronize on both sides, MAX over ranks.  K = 20 steps are 1.7 ms, too
-    # short for one sample to be robust (clock ramps, a neighbour on the host), so the batch is repeated --batches times back to
-    # back and the line reports the MEDIAN batch (every batch is in "timing").
-    walls, kmss = [], []
-    for _ in range(max(1, args.batches)):
+    # The timed region is EXACTLY --steps steps.  A timed batch = a run of them between barrier + synchronize on both sides, MAX over
+    # ranks.  One sample of 20 steps (1.4 ms) is not robust (clock ramps, a neighbour on the host), so where --steps allows the steps
+    # are cut into up to --batches batches of at least MIN_BATCH_STEPS steps, back to back, and the line reports the MEDIAN batch's
+    # time per step (every batch is in "timing"); --steps 20 is one batch.
+    nbatch = max(1, min(args.batches, args.steps // MIN_BATCH_STEPS))
+    sizes = [args.steps // nbatch + (1 if i < args.steps % nbatch else 0) for i in range(nbatch)]
+    steps_ms, kmss = [], []
+    for n in sizes:
         barrier()
         t0 = time.perf_counter()
-        kms = run(plan, args.steps)     # K launches, HIP events on the launch stream around them
+        kms = run(plan, n)              # n launches, HIP events on the launch stream around them
         barrier()
         w = time.perf_counter() - t0
         if dist is not None:
             t = torch.tensor([w, kms], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             w, kms = t[0].item(), t[1].item()
-        walls.append(w); kmss.append(kms)
-    order = sorted(range(len(walls)), key=lambda i: walls[i])
-    mid = order[len(order) // 2]
-    wall, kernel_ms = walls[mid], kmss[mid]
-    timing = {"batches": len(walls), "steps_per_batch": args.steps, "statistic": "median batch (wall clock around exactly --steps steps)",
-              "batch_ms_per_step_min_median_max": [min(walls) / args.steps * 1e3, wall / args.steps * 1e3, max(walls) / args.steps * 1e3],
+        steps_ms.append(w / n * 1e3); kmss.append(kms)
+    last_set = (sizes[-1] - 1) % S      # (every batch starts at set 0: the matrix the last timed step factorised)
+    order = sorted(range(nbatch), key=lambda i: steps_ms[i])
+    mid = order[nbatch // 2]
+    ms_per_step, kernel_ms = steps_ms[mid], kmss[mid]
+    timing = {"batches": nbatch, "steps_per_batch": [min(sizes), max(sizes)], "timed_steps": sum(sizes),
+              "statistic": "median batch (wall clock around its steps, per step); the batches together are exactly --steps steps",
+              "batch_ms_per_step_min_median_max": [min(steps_ms), ms_per_step, max(steps_ms)],
               "kernel_us_min_median_max": [min(kmss) * 1e3, sorted(kmss)[len(kmss) // 2] * 1e3, max(kmss) * 1e3],
-              "first_batch_ms_per_step": walls[0] / args.steps * 1e3,
-              "note": "value / ms_per_step are the MEDIAN batch since round 4; rounds 1-3 reported one batch of --steps steps: "
-                      "first_batch_ms_per_step is that statistic for like-for-like comparison across rounds",
-              "timed_region_ms_total": sum(walls) * 1e3}
+              "first_batch_ms_per_step": steps_ms[0],
+              "note": "value / ms_per_step are the MEDIAN batch since round 4; rounds 1-3 reported one batch of --steps steps, rounds 4-6 "
+                      "the median of 25 batches of --steps steps each",
+              "timed_region_ms_total": sum(m * n for m, n in zip(steps_ms, sizes))}
+
+    # ---- outside the timed region: what the last timed step wrote, for a comparison of two builds output for output
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, np, torch, dev, qv[last_set * nq:(last_set + 1) * nq], rv[last_set * nr:(last_set + 1) * nr],
+                     pm[last_set * ncol:(last_set + 1) * ncol])
 
     # ---- outside the timed region: the kernel instantiation that was just timed (tau not stored) against the oracle
     checked = None
-    if not args.no_check and rank == 0:
+    if args.full and not args.no_check and rank == 0:
         from oracle import oracle as orc
         nchk = 500
         host = tiles[:nchk * BR * BC].cpu().numpy()
@@ -297,7 +324,7 @@ def main():
 
     # ---- steady state (N = 1): the same kernel on 160000 tiles per launch, where the three-round tail of 10000 tiles vanishes
     steady = None
-    if world == 1 and not args.no_steady:
+    if world == 1 and args.full and not args.no_steady:
         nb_big = 160000
         pbig = make_plan(nb_big)
         tb = torch.rand(nb_big * BR * BC, generator=g, device=dev, dtype=torch.float64) * 4.5 + 0.5
@@ -314,7 +341,7 @@ def main():
 
     # ---- strong scaling (N > 1): one B-block matrix over the ranks, R and perm gathered on rank 0 inside the timed region
     strong = None
-    if dist is not None and world > 1 and not args.no_strong:
+    if dist is not None and world > 1 and args.full and not args.no_strong:
         strong = strong_scaling(args, ctx, dev, dist, backend, rank, world, torch, np)
         if args.mixed_blocks > 0:
             strong["configs4_mixed"] = strong_mixed(args, ctx, dev, dist, backend, rank, world, torch, np)
@@ -323,7 +350,7 @@ def main():
 
     # ---- another BASELINE configuration on this GPU (N = 1; reported next to the headline, never as `value`)
     other = None
-    if world == 1 and not args.no_other:
+    if world == 1 and args.full and not args.no_other:
         # (auxiliary legs: a failure in one of them is reported in its place and does not cost the line)
         def leg(fn, *a):
             try:
@@ -341,7 +368,7 @@ def main():
 
     # ---- end to end with host buffers (N = 1): tiles over PCIe in, Q / R / perm back (never the headline value)
     e2e = None
-    if world == 1 and not args.no_e2e:
+    if world == 1 and args.full and not args.no_e2e:
         ht = tiles[:tl].cpu().numpy()
         hq = np.empty(nq); hr = np.empty(nr); hp = np.empty(ncol, np.int32)
         lib = capi.lib()
@@ -356,7 +383,7 @@ def main():
                        "not the headline value (inputs there are resident in HBM)"}
 
     if rank == 0:
-        fact_per_s = world * args.steps / wall
+        fact_per_s = world * 1e3 / ms_per_step
         bytes_per_launch = BYTES_PER_TILE * BLOCKS
         achieved = bytes_per_launch / (kernel_ms * 1e-3) / 1e9
         capi.lib().qrk_bd_kernel_name.restype = C.c_char_p
@@ -370,7 +397,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
-            "ms_per_step": wall / args.steps * 1e3,
+            "ms_per_step": ms_per_step,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -416,6 +443,17 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(path, np, torch, dev, q, r, p):
+    """--dump-outputs: Q (32 x 32 per tile), the packed R (528 per tile) and the column permutation (32 per tile) of ONE matrix, as a
+    caller of factorize() receives them, for DUMP_TILES tiles drawn once with a fixed seed (sample_tiles.npy says which), as float64."""
+    os.makedirs(path, exist_ok=True)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(BLOCKS, DUMP_TILES, replace=False))
+    sel = torch.from_numpy(idx).to(dev)
+    np.save(os.path.join(path, "sample_tiles.npy"), idx.astype(np.float64))
+    for name, t in (("Q", q), ("R", r), ("perm", p)):
+        np.save(os.path.join(path, name + ".npy"), t.view(BLOCKS, -1)[sel].cpu().numpy().astype(np.float64))
 
 
 def strong_scaling(args, ctx, dev, dist, backend, rank, world, torch, np):

@@ -6,7 +6,7 @@ ROOT=$(pwd)
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/small" -- python3 "$ROOT/tools/small_probe_big.py" > "$ROOT/$OUT/small.log" 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/bench" -- python3 "$ROOT/bench.py" --no-cpu-baseline > "$ROOT/$OUT/bench.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/bench" -- python3 "$ROOT/bench.py" --full --no-cpu-baseline > "$ROOT/$OUT/bench.log" 2>&1
 cd "$ROOT"
 for d in small bench; do
   f=$(find "$OUT/$d" -name "*kernel_stats.csv" | head -1)
