@@ -344,6 +344,7 @@ class BlockDiagonalSparseQR {
         m_Q.resize(rows, rows);
         m_R.resize(rows, cols);
         m_Qsynced = m_Rsynced = false;
+        m_qless = false;
         m_outputPerm_c.setIdentity(cols);
         reserve(m_dtiles, m_ctiles, tl * (int64_t)sizeof(double));
         reserve(m_dq, m_cq, nq * (int64_t)sizeof(double));
@@ -360,11 +361,56 @@ class BlockDiagonalSparseQR {
         m_isInitialized = true;
         m_factorizationIsok = true;
     }
+    // factorize(mat) and solve(B) in ONE pass that never forms Q (qrk_bd_factorize_rhs): what an LM loop reads every iteration is
+    // R, the column permutation and Q^T f (examples/ellipse_fitting.cpp:126-142).  B: rows x nrhs, column-major; returns x
+    // (cols x nrhs) and, when asked, Q^T B in *QtB.  Runs after analyzePattern() and re-uses the plan like factorize().  Afterwards
+    // matrixR() / colsPermutation() / rank() / info() / solveR() work; matrixQ() / applyQ() / applyQt() / solve() throw ("factorised
+    // without Q") until the next factorize() or compute().
+    Vector factorizeAndSolve(const MatrixType& mat, const Vector& B, Vector* QtB = 0) {
+        assert(m_analysisIsok && "analyzePattern() should be called first");
+        int64_t tl, nq, nr;
+        check(qrk_bd_plan_sizes(m_plan, &tl, &nq, &nr));
+        const Index rows = mat.rows(), cols = mat.cols();
+        assert(rows > 0 && (Index)B.size() % rows == 0 && "SparseQR::solve() : invalid number of rows in the right hand side matrix");
+        const int64_t nrhs = (int64_t)B.size() / rows;
+        m_nq = nq; m_nr = nr;
+        m_Q.resize(rows, rows);
+        m_R.resize(rows, cols);
+        m_Qsynced = m_Rsynced = false;
+        m_isInitialized = m_factorizationIsok = false;
+        m_qless = true;
+        m_outputPerm_c.setIdentity(cols);
+        reserve(m_dtiles, m_ctiles, tl * (int64_t)sizeof(double));
+        reserve(m_dr, m_cr, nr * (int64_t)sizeof(double));
+        reserve(m_dperm, m_cperm, cols * (int64_t)sizeof(int32_t));
+        check(qrk_memcpy(m_handle, m_dtiles, mat.tiles().data(), tl * (int64_t)sizeof(double), 0));
+        Vector x((size_t)(nrhs * cols), 0.0);
+        DeviceVec b(*this, B), dx(*this, x.size()), dy(*this, QtB ? B.size() : (size_t)1);
+        check(qrk_bd_factorize_rhs(m_plan, (const double*)m_dtiles, b.ptr(), nrhs, (double*)m_dr, (int32_t*)m_dperm, 0,
+                                   QtB ? dy.ptr() : (double*)0, dx.ptr(), QRK_MEM_DEVICE));
+        qrk_info info; int64_t rank;
+        check(qrk_bd_info(m_plan, &info, &rank));
+        m_info = (ComputationInfo)info;
+        if (m_info != Success) return x;   // InvalidInput: nothing was written, as in factorize()
+        check(qrk_memcpy(m_handle, m_outputPerm_c.indices().data(), m_dperm, cols * (int64_t)sizeof(int32_t), 1));
+        dx.download(x);
+        if (QtB) { QtB->assign(B.size(), 0.0); dy.download(*QtB); }
+        m_nonzeropivots = rank;
+        m_isInitialized = true;
+        m_factorizationIsok = true;
+        return x;
+    }
+    // analyzePattern() + factorizeAndSolve(): compute() followed by solve(B), without Q
+    Vector computeAndSolve(const MatrixType& mat, const Vector& B, Vector* QtB = 0, const PermutationType& rowPerm = PermutationType()) {
+        analyzePattern(mat, rowPerm);
+        return factorizeAndSolve(mat, B, QtB);
+    }
+    bool hasQ() const { return !m_qless; }
 
     Index rows() const { return m_R.rows(); }
     Index cols() const { return m_R.cols(); }
     const MatrixRType& matrixR() const { syncR(); return m_R; }
-    MatrixQType matrixQ() const { syncQ(); return m_Q; }   // by value, as the reference (:235-237)
+    MatrixQType matrixQ() const { needQ("matrixQ()"); syncQ(); return m_Q; }   // by value, as the reference (:235-237)
     const PermutationType& colsPermutation() const { assert(m_isInitialized && "Decomposition is not initialized."); return m_outputPerm_c; }
     const PermutationType& rowsPermutation() const { assert(m_isInitialized && "Decomposition is not initialized."); return m_rowPerm; }
     Index rank() const { assert(m_isInitialized && "The factorization should be called first, use compute()"); return m_nonzeropivots; }
@@ -374,6 +420,7 @@ class BlockDiagonalSparseQR {
     bool _solve_impl(const Vector& B, Vector& dest) const {
         assert(m_isInitialized && "The factorization should be called first, use compute()");
         assert((Index)B.size() % rows() == 0 && "SparseQR::solve() : invalid number of rows in the right hand side matrix");
+        needQ("solve()");
         const int64_t nrhs = (int64_t)B.size() / rows();
         dest.assign((size_t)(nrhs * cols()), 0.0);
         DeviceVec b(*this, B), x(*this, dest.size());
@@ -396,6 +443,7 @@ class BlockDiagonalSparseQR {
     }
     // matrixQ().transpose() * B on the device (test/test-qrkit.cpp:187)
     Vector applyQt(const Vector& B) const {
+        needQ("applyQt()");
         const int64_t nrhs = (int64_t)B.size() / rows();
         Vector y(B.size());
         DeviceVec b(*this, B), dy(*this, y.size());
@@ -405,6 +453,7 @@ class BlockDiagonalSparseQR {
     }
     // matrixQ() * B on the device (the product with the explicit m_Q)
     Vector applyQ(const Vector& B) const {
+        needQ("applyQ()");
         const int64_t nrhs = (int64_t)B.size() / rows();
         Vector y(B.size());
         DeviceVec b(*this, B), dy(*this, y.size());
@@ -415,6 +464,7 @@ class BlockDiagonalSparseQR {
     // The same three steps on device pointers (rows x nrhs / cols x nrhs, contiguous columns; in and out must not alias); they
     // return when the result is in memory.  BlockAngularSparseQR keeps Q1^T J2 on the device with them.
     void applyQDevice(const double* d_in, int64_t nrhs, double* d_out, bool transpose) const {
+        needQ("applyQDevice()");
         check(transpose ? qrk_bd_apply_qt(m_plan, (const double*)m_dq, d_in, nrhs, d_out, QRK_MEM_DEVICE)
                         : qrk_bd_apply_q(m_plan, (const double*)m_dq, d_in, nrhs, d_out, QRK_MEM_DEVICE));
         check(qrk_synchronize(m_handle));
@@ -427,6 +477,10 @@ class BlockDiagonalSparseQR {
   protected:
     void check(qrk_status st) const {
         if (st != QRK_STATUS_OK) throw std::runtime_error(std::string("qrkit: ") + qrk_last_error(m_handle));
+    }
+    // the last factorisation was factorizeAndSolve(): there is no Q array to read
+    void needQ(const char* what) const {
+        if (m_qless) throw std::runtime_error(std::string("qrkit: ") + what + ": factorised without Q (factorizeAndSolve); call factorize() or compute()");
     }
     // scoped device vector of doubles for a right-hand side / a result
     struct DeviceVec {
@@ -474,6 +528,7 @@ class BlockDiagonalSparseQR {
     void* m_dtiles = 0; void* m_dq = 0; void* m_dr = 0; void* m_dperm = 0;     // device-resident tiles, factors, permutation
     int64_t m_ctiles = 0, m_cq = 0, m_cr = 0, m_cperm = 0, m_nq = 0, m_nr = 0;
     mutable bool m_Qsynced = false, m_Rsynced = false;
+    bool m_qless = false;
     mutable ComputationInfo m_info;
     mutable MatrixRType m_R;
     mutable MatrixQType m_Q;

@@ -209,6 +209,28 @@ qrk_status qrk_bd_solve(qrk_bd_plan plan, const double* q_vals, const double* r_
 qrk_status qrk_bd_solve_r(qrk_bd_plan plan, const double* r_vals, const double* y, int64_t nrhs, double* z,
                           qrk_memspace space);
 
+/* factorize() + the Q^T b and back substitution of _solve_impl (BlockDiagonalSparseQR.h:257-280) in one pass, Q never
+ * formed in device memory: what a Levenberg-Marquardt caller needs every iteration (R, the column permutation, Q^T f;
+ * examples/ellipse_fitting.cpp:126-142).
+ *   tiles   [tiles_len]         in : as qrk_bd_factorize
+ *   b       [mat_rows x nrhs]   in : column-major, ld = mat_rows
+ *   r_vals, perm, hcoeffs       out: what qrk_bd_factorize writes for this plan (hcoeffs may be NULL)
+ *   qtb     [mat_rows x nrhs]   out, may be NULL: what qrk_bd_apply_qt gives (the plan's Q format decides the row order:
+ *                                    FullQ [U.. | N..]); trailing identity rows copy b.  Must not overlap b.
+ *   x       [mat_cols x nrhs]   out, may be NULL: what qrk_bd_solve gives (FullQ plans only: QRK_STATUS_UNSUPPORTED otherwise)
+ * At least one of qtb / x must be given.  qrk_bd_info afterwards as after qrk_bd_factorize.
+ * Uniform plans of tiles with 1 or 2 columns and at most 16 rows (up to 4 right-hand sides) and uniform 32 x 32 plans
+ * (up to 32 right-hand sides, 16-byte aligned arrays) run kernels that never form Q; every other plan factorizes into a
+ * Q scratch owned by the plan (nnz_q doubles, allocated by the first such call: QRK_STATUS_ALLOC_FAILED if that fails)
+ * and applies it.  QRK_MEM_DEVICE: enqueued on the handle's stream; QRK_MEM_HOST: staged like qrk_bd_factorize. */
+qrk_status qrk_bd_factorize_rhs(qrk_bd_plan plan, const double* tiles, const double* b, int64_t nrhs,
+                                double* r_vals, int32_t* perm, double* hcoeffs, double* qtb, double* x,
+                                qrk_memspace space);
+
+/* Name of the kernel qrk_bd_factorize_rhs runs on this plan for nrhs right-hand sides (aligned arrays), or a string
+ * that contains "fallback" when the plan takes the explicit-Q route.  The pointer is static, like qrk_bd_kernel_name. */
+const char* qrk_bd_rhs_kernel_name(qrk_bd_plan plan, int64_t nrhs);
+
 /* --------------------------------------------- dense right-block solver (angular) */
 
 /* A single dense Householder QR with implicit Q: the _BlockQRSolverRight of

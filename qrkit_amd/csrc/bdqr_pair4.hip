@@ -22,6 +22,8 @@
 // Decisions and the exact path exactly as bdqr_pair.hip ("Decisions and the exact path" there): integer arg-max on the high words
 // with a filter, margins, LAWN-176 band, degenerate reflector, noise-level pivot; a flagged tile is redone by the wave itself with the
 // exact-arithmetic routine after its rounds (working copy in a global scratch: the LDS of this kernel is too small for it).
+// A second kernel at the end of the file, bdqr_pair4_rhs_kernel, is the Q-less form for callers that only solve: same phase 1, phase 2
+// turns right-hand sides into Q^T b instead of the identity into Q.
 #include "qrk_device.h"
 #include "bdqr_exact_tile.h"
 
@@ -655,6 +657,241 @@ bdqr_pair4_kernel(int64_t num_tiles, const double* __restrict__ tiles, double* _
     }
 }
 
+// ---- the right-hand-side form: factorise and solve WITHOUT Q (behind qrk_bd_factorize_rhs) ---------------------------------------------
+// What a caller that only solves needs of Q is Q^T b (_solve_impl, BlockDiagonalSparseQR.h:266).  Phase 2's machinery gives it directly: a
+// right-hand side held as one lane's 32 row registers is transformed by back_step<K> in ASCENDING K -- H_K is symmetric, so that is
+// H_31 ... H_0 b = Q^T b.  Lane j of each half carries right-hand side j (up to 32).  The loads, phase 1 and the stores of R, the
+// permutation and tau are bdqr_pair4_kernel's statements (without its diagnostic switches); the 8 KB of Q per tile are neither formed
+// nor stored.  A flagged tile goes onto the redo list (bdqr_qless.hip redoes it in Eigen's operation order, Q in LDS).
+struct P4Rhs {
+    const double* b;        // mat_rows x nrhs, column-major
+    double* qtb;            // same shape, may be null: Q^T b (32 x 32 tiles cover rows and columns alike: both Q formats place entry k of
+                            // tile t at 32 t + k)
+    double* xtop;           // mat_cols x nrhs, may be null: the same 32 entries at the tile's own columns (qless_backsolve32_kernel
+                            // turns them into x in place)
+    int64_t mat_rows, mat_cols;
+    int nrhs;               // 1 .. 32
+    int32_t* redo_count;
+    int32_t* redo_ids;
+};
+
+//
+// One or two right-hand sides (NR = 1, 2: the Levenberg-Marquardt step) need no phase 2 at all.  Each is held ONE ENTRY PER LANE (lane
+// j of a half: row j) and follows the columns of A through phase 1: after step K, y <- H_K y with the reflector that step just left
+// in LDS -- one product per lane, one sum over the half, one FMA.  At the end lane j holds (Q^T b)(j) and, from phase 1, column
+// kstep of R in its row registers: the back substitution runs row by row in the wave (entry (k, p) of R is row register k of the lane
+// whose kstep is p: a static register index), and since the column chosen at step p is the lane's own, x(32 t + j) is lane j's
+// unknown -- Q^T b and x leave as two coalesced stores.  NR = 0 is the general form above (3 .. 32 right-hand sides).
+namespace p4 {
+
+// sum over each half of the wave, the same bits in every lane of the half
+__device__ __forceinline__ double half32_sum(double v)
+{
+    v = row16_sum(v);
+    const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(v), (unsigned)__double2loint(v), false, false);
+    const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(v), (unsigned)__double2hiint(v), false, false);
+    return __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
+}
+
+// y <- H_K y for the right-hand sides held one entry per lane: u = [0 .. 0; s; x_tail] as step<K> published it, gamma as in step<K>
+template <int K, int NR>
+__device__ __forceinline__ void rhs_step(double (&y)[NR], const double* hl, const int j)
+{
+    __builtin_amdgcn_wave_barrier();
+    const double s = *(const volatile lds_f64*)(&hl[L_S + K]);
+    const double ngp = *(const volatile lds_f64*)(&hl[L_NG + K]);
+    double u = j == K ? s : 0.0;
+    if (K + 1 < WR) {
+        const double* vcol = hl + L_V + cb(K) - (K & ~1);
+        const double xv = *(const volatile lds_f64*)(vcol + (j > K ? j : K));
+        if (j > K) u = xv;
+    }
+#pragma unroll
+    for (int n = 0; n < NR; ++n) {
+        const double ngam = half32_sum(u * y[n]) * -ngp;
+        y[n] = fma(u, ngam, y[n]);
+    }
+}
+
+}  // namespace p4
+
+template <bool PIVOT, bool HC, bool OWN, int NR>
+__global__ void __launch_bounds__(64, 4)
+bdqr_pair4_rhs_kernel(int64_t num_tiles, const double* __restrict__ tiles, double* __restrict__ r_vals, int32_t* __restrict__ perm,
+                      double* __restrict__ hcoeffs, P4Rhs rhs)
+{
+    using namespace p4;
+    __shared__ __attribute__((aligned(16))) double lds[2 * L_HALF];
+    const int64_t npairs = (num_tiles + 1) / 2;
+    const bool steady = npairs >= 3 * (int64_t)gridDim.x;
+    const bool direct = npairs >= 2 * (int64_t)gridDim.x || 2 * npairs <= (int64_t)gridDim.x;     // (see bdqr_pair4_kernel's loads)
+    for (int64_t pi = blockIdx.x; pi < npairs; pi += gridDim.x) {
+        int lane = threadIdx.x;
+        asm volatile("" : "+v"(lane));
+        const int half = lane >> 5, j = lane & 31;
+        double* hl = lds + half * L_HALF;
+        const int64_t t = 2 * pi + half;
+        const bool valid = t < num_tiles;
+        Lane st;
+        st.lane = lane; st.j = j; st.half = half; st.unclearm = 0ull; st.kstep = 0; st.a2 = 0.0; st.livemask = ~0ull;
+        // (NR > 0) the right-hand sides, row j of the tile's segment in lane j: requested with the tile, used from step 0 on
+        double y[NR > 0 ? NR : 1];
+        if constexpr (NR > 0) {
+            const double* src = rhs.b + (valid ? t : 2 * pi) * 32 + j;
+#pragma unroll
+            for (int n = 0; n < NR; ++n) y[n] = src[(int64_t)n * rhs.mat_rows];
+        }
+        {
+            // =============== phase 1: A -> R ===============
+            if (steady) __builtin_amdgcn_s_setprio(2);
+            double a[WR];
+            if (direct) {
+                typedef double d2u __attribute__((ext_vector_type(2), aligned(8)));
+                const double* src = tiles + (valid ? t : 2 * pi) * 1024 + j * 32;
+#pragma unroll
+                for (int i = 0; i < WR; i += 2) {
+                    const d2u v = *reinterpret_cast<const d2u*>(src + i);
+                    a[i] = v.x; a[i + 1] = v.y;
+                }
+                if (!valid) {
+#pragma unroll
+                    for (int i = 0; i < WR; ++i) a[i] = (i == j) ? (double)(64 - j) : 0.0;
+                }
+            } else {
+                typedef double d2u __attribute__((ext_vector_type(2), aligned(8)));
+                typedef double d2a __attribute__((ext_vector_type(2), aligned(16)));
+                d2u ld0[8], ld1[8];
+                const int64_t t0 = 2 * pi, t1 = 2 * pi + 1;
+                const double* s0 = tiles + t0 * 1024 + 2 * lane;
+                const double* s1 = tiles + (t1 < num_tiles ? t1 : t0) * 1024 + 2 * lane;
+#pragma unroll
+                for (int m = 0; m < 8; ++m) ld0[m] = QRK_P4_LOAD(reinterpret_cast<const d2u*>(s0 + 128 * m));
+#pragma unroll
+                for (int m = 0; m < 8; ++m) ld1[m] = QRK_P4_LOAD(reinterpret_cast<const d2u*>(s1 + 128 * m));
+                double* sw = lds + (lane >> 4) * STAGE_LD + 2 * (lane & 15);
+#pragma unroll
+                for (int m = 0; m < 8; ++m) *reinterpret_cast<d2a*>(sw + 4 * m * STAGE_LD) = d2a{ld0[m].x, ld0[m].y};
+                __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                for (int i = 0; i < WR; i += 2) {
+                    const d2a v = *reinterpret_cast<const d2a*>(lds + j * STAGE_LD + i);
+                    a[i] = v.x; a[i + 1] = v.y;
+                }
+                __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                for (int m = 0; m < 8; ++m) *reinterpret_cast<d2a*>(sw + 4 * m * STAGE_LD) = d2a{ld1[m].x, ld1[m].y};
+                __builtin_amdgcn_wave_barrier();
+                if (half == 1) {
+#pragma unroll
+                    for (int i = 0; i < WR; i += 2) {
+                        const d2a v = *reinterpret_cast<const d2a*>(lds + j * STAGE_LD + i);
+                        a[i] = valid ? v.x : ((i == j) ? (double)(64 - j) : 0.0);
+                        a[i + 1] = valid ? v.y : ((i + 1 == j) ? (double)(64 - j) : 0.0);
+                    }
+                }
+                __builtin_amdgcn_wave_barrier();
+            }
+            {
+                double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+                for (int i = 0; i < WR; i += 2) { s0 = fma(a[i], a[i], s0); s1 = fma(a[i + 1], a[i + 1], s1); }
+                st.nu2 = s0 + s1;
+                st.thr = st.nu2 * THR_HI;
+            }
+#define QRK_P4_STEP(K) step<K, PIVOT, HC, OWN>(a, hl, st); if constexpr (NR > 0) rhs_step<K, NR>(y, hl, j);
+            QRK_P4_0_31(QRK_P4_STEP)
+#undef QRK_P4_STEP
+            int ln = threadIdx.x;
+            asm volatile("" : "+v"(ln));
+            if (valid) {
+                const int p = st.kstep, jj = ln & 31;
+                const int cbase = (int)(t * 32);
+                perm[cbase + p] = cbase + jj;
+                double* dst = r_vals + t * 528 + ((p * (p + 1)) >> 1);
+                typedef double d2u __attribute__((ext_vector_type(2), aligned(8)));
+#pragma unroll
+                for (int i = 0; i < WR; i += 2) {
+                    if (i + 1 <= p) QRK_P4_STORE((d2u{a[i], a[i + 1]}), reinterpret_cast<d2u*>(dst + i));
+                    else if (i == p) QRK_P4_STORE(a[i], dst + i);
+                }
+                if (HC && hcoeffs) hcoeffs[cbase + jj] = lds[(ln >> 5) * L_HALF + L_TAU + jj];
+            }
+            if constexpr (NR > 0) {
+                // ---- x = P R^-1 (Q^T b)(0:32), row by row from the last: the lane whose column was chosen at step p holds R(0:p, p) and
+                // solves z(p); P z puts z(p) at the lane's own column (the permutation splice above)
+                const int jj = ln & 31, p = st.kstep;
+                double diag = a[0];
+#pragma unroll
+                for (int i = 1; i < WR; ++i) diag = (p == i) ? a[i] : diag;
+                const double invd = 1.0 / diag;
+                double yp[NR], z[NR];
+#pragma unroll
+                for (int n = 0; n < NR; ++n) { yp[n] = bpermute_f64((((ln >> 5) << 5) + p) << 2, y[n]); z[n] = 0.0; }
+#define QRK_P4_BSUB(K)                                                                       \
+                _Pragma("unroll") for (int n = 0; n < NR; ++n) {                             \
+                    const double prod = a[K] * z[n];                                         \
+                    const double sum = half32_sum(p > (K) ? prod : 0.0);                     \
+                    if (p == (K)) z[n] = (yp[n] - sum) * invd;                               \
+                }
+                QRK_P4_31_0(QRK_P4_BSUB)
+#undef QRK_P4_BSUB
+                if (valid) {
+#pragma unroll
+                    for (int n = 0; n < NR; ++n) {
+                        if (rhs.qtb) rhs.qtb[(int64_t)n * rhs.mat_rows + t * 32 + jj] = y[n];
+                        if (rhs.xtop) rhs.xtop[(int64_t)n * rhs.mat_cols + t * 32 + jj] = z[n];
+                    }
+                }
+            }
+        }
+        // a decision inside its error margin, anywhere in the half: the tile is redone by the exact path behind this launch
+        {
+            const unsigned long long um = st.unclearm;
+            const bool f = half ? (um >> 32) != 0ull : (um & 0xffffffffull) != 0ull;
+            if (f && valid && j == 0) rhs.redo_ids[atomicAdd(rhs.redo_count, 1)] = (int32_t)t;
+        }
+        if constexpr (NR == 0) {
+            // =============== phase 2: Q^T b = H_31 ... H_0 b, forward ===============
+            if (steady) __builtin_amdgcn_s_setprio(0);
+            int ln = threadIdx.x;
+            asm volatile("" : "+v"(ln));
+            const int jj = ln & 31;
+            const double* hl2 = lds + (ln >> 5) * L_HALF;
+            typedef double d2u __attribute__((ext_vector_type(2), aligned(8)));
+            // lane jj of each half: right-hand side jj, rows 32 t .. 32 t + 31 (the lanes past nrhs carry a copy of right-hand side 0,
+            // which is not stored; the missing partner of an odd last tile reads its neighbour's rows)
+            double q[WR];
+            {
+                const double* src = rhs.b + (int64_t)(jj < rhs.nrhs ? jj : 0) * rhs.mat_rows + (valid ? t : 2 * pi) * 32;
+#pragma unroll
+                for (int i = 0; i < WR; i += 2) {
+                    const d2u v = *reinterpret_cast<const d2u*>(src + i);
+                    q[i] = v.x; q[i + 1] = v.y;
+                }
+            }
+            double sv[2], ngv[2];
+#pragma unroll
+            for (int m = 0; m < 2; ++m) { sv[m] = hl2[L_S + 16 * m + (ln & 15)]; ngv[m] = hl2[L_NG + 16 * m + (ln & 15)]; }
+#define QRK_P4_FWD(K) back_step<K>(q, hl2, ln, sv, ngv);
+            QRK_P4_0_31(QRK_P4_FWD)
+#undef QRK_P4_FWD
+            if (valid && jj < rhs.nrhs) {
+                if (rhs.qtb) {
+                    double* dst = rhs.qtb + (int64_t)jj * rhs.mat_rows + t * 32;
+#pragma unroll
+                    for (int i = 0; i < WR; i += 2) *reinterpret_cast<d2u*>(dst + i) = d2u{q[i], q[i + 1]};
+                }
+                if (rhs.xtop) {
+                    double* dst = rhs.xtop + (int64_t)jj * rhs.mat_cols + t * 32;
+#pragma unroll
+                    for (int i = 0; i < WR; i += 2) *reinterpret_cast<d2u*>(dst + i) = d2u{q[i], q[i + 1]};
+                }
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
 // step<.., OWN> (the pivot lane's own norm) for launches of more than one round of the resident waves, see step; QRK_P4_OWN=0 / 1 forces
 // the choice (diagnostic)
 bool bdqr_pair4_own_norm(int64_t num_tiles, int num_wg)
@@ -683,6 +920,33 @@ hipError_t launch_bdqr_pair4(int64_t num_tiles, int pivoting, const double* tile
     else { if (hcoeffs) QRK_P4_LAUNCH2(false, true); else QRK_P4_LAUNCH2(false, false); }
 #endif
 #undef QRK_P4_LAUNCH2
+#undef QRK_P4_LAUNCH
+    return hipGetLastError();
+}
+
+// The right-hand-side form (bdqr_pair4_rhs_kernel): R, permutation and tau as above; Q^T b and its top (see P4Rhs) instead of Q.
+// With at most BDQR_PAIR4_RHS_INLANE right-hand sides the kernel finishes x itself (nothing to launch behind it but the redo pass).
+bool bdqr_pair4_rhs_solves(int nrhs) { return nrhs >= 1 && nrhs <= BDQR_PAIR4_RHS_INLANE; }
+
+hipError_t launch_bdqr_pair4_rhs(int64_t num_tiles, int pivoting, const double* tiles, const double* b, int nrhs, int64_t mat_rows,
+                                 int64_t mat_cols, double* r_vals, int32_t* perm, double* hcoeffs, double* qtb, double* xtop, int num_wg,
+                                 int32_t* redo_count, int32_t* redo_ids, hipStream_t stream)
+{
+    if (num_tiles <= 0) return hipSuccess;
+    if (nrhs < 1 || nrhs > 32 || !b || !redo_count || !redo_ids) return hipErrorInvalidValue;
+    const int64_t npairs = (num_tiles + 1) / 2;
+    const int64_t nwg = npairs < num_wg ? npairs : num_wg;
+    const dim3 grid((unsigned)nwg), block(64);
+    const bool own = bdqr_pair4_own_norm(num_tiles, num_wg);
+    const P4Rhs rhs{b, qtb, xtop, mat_rows, mat_cols, nrhs, redo_count, redo_ids};
+    static_assert(BDQR_PAIR4_RHS_INLANE == 2, "one instantiation per in-lane count below");
+#define QRK_P4_LAUNCH(P, H, L, N) hipLaunchKernelGGL((bdqr_pair4_rhs_kernel<P, H, L, N>), grid, block, 0, stream, num_tiles, tiles, r_vals, perm, hcoeffs, rhs)
+#define QRK_P4_LAUNCH3(P, H, L) do { if (nrhs == 1) QRK_P4_LAUNCH(P, H, L, 1); else if (nrhs == 2) QRK_P4_LAUNCH(P, H, L, 2); else QRK_P4_LAUNCH(P, H, L, 0); } while (0)
+#define QRK_P4_LAUNCH2(P, H) do { if (own) QRK_P4_LAUNCH3(P, H, true); else QRK_P4_LAUNCH3(P, H, false); } while (0)
+    if (pivoting) { if (hcoeffs) QRK_P4_LAUNCH2(true, true); else QRK_P4_LAUNCH2(true, false); }
+    else { if (hcoeffs) QRK_P4_LAUNCH2(false, true); else QRK_P4_LAUNCH2(false, false); }
+#undef QRK_P4_LAUNCH2
+#undef QRK_P4_LAUNCH3
 #undef QRK_P4_LAUNCH
     return hipGetLastError();
 }

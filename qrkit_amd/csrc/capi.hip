@@ -106,6 +106,7 @@ struct qrk_bd_plan_s {
     double* d_exact_ws = nullptr;        // working copies of tiles too large for the exact kernel's LDS
     int64_t exact_ws_stride = 0;
     int exact_num_wg = 0, exact_maxr = 0, exact_maxc = 0;
+    double* d_q_scratch = nullptr;       // qrk_bd_factorize_rhs on a plan without a Q-less kernel: nnz_q doubles, allocated on first use
 };
 
 // One size class of the mid-size tiles: on chip (bdqr_reg.hip) when all of its tiles are wider than 64 columns, else bdqr_col.hip
@@ -490,6 +491,71 @@ qrk_status enqueue_factorize(qrk_bd_plan_s* p, const double* tiles, double* q, d
     return QRK_STATUS_OK;
 }
 
+// The kernel that serves qrk_bd_factorize_rhs on this plan with this many right-hand sides, by the conditions that pick its explicit-Q
+// sibling in enqueue_factorize: RHS_THIN = bdqr_thin_rhs.hip, RHS_PAIR4 = the right-hand-side form of bdqr_pair4.hip (the arrays of the
+// call must also be 16-byte aligned), RHS_FALLBACK = factorize + Q^T b + solve through the plan's own Q scratch.
+enum RhsRoute { RHS_FALLBACK = 0, RHS_THIN = 1, RHS_PAIR4 = 2 };
+RhsRoute rhs_route(const qrk_bd_plan_s* p, int64_t nrhs)
+{
+    const qrk_handle h = p->h;
+    if (h->force_exact || !p->uniform || p->landscape || p->B <= 0 || !p->d_redo) return RHS_FALLBACK;
+    if (p->max_dim <= 16 && p->r >= p->c && p->c <= 2 && h->use_small_kernel && h->use_thin_kernel)
+        return qrk::bdqr_thin_rhs_supported(p->r, p->c, nrhs) ? RHS_THIN : RHS_FALLBACK;
+    if (p->d_p4_scratch && nrhs >= 1 && nrhs <= 32) return RHS_PAIR4;
+    return RHS_FALLBACK;
+}
+
+// factorize() and the Q^T b / back substitution / permutation of _solve_impl (BlockDiagonalSparseQR.h:257-280) on the handle's stream,
+// device pointers; qtb and x may each be null (not both).  No host synchronisation on the Q-less routes (the fallback allocates the
+// plan's Q scratch on its first use).
+qrk_status enqueue_factorize_rhs(qrk_bd_plan_s* p, const double* tiles, const double* b, int64_t nrhs, double* r, int32_t* perm, double* hc,
+                                 double* qtb, double* x)
+{
+    qrk_handle h = p->h;
+    RhsRoute route = rhs_route(p, nrhs);
+    if (route == RHS_PAIR4 && ((reinterpret_cast<uintptr_t>(tiles) | reinterpret_cast<uintptr_t>(r) | reinterpret_cast<uintptr_t>(b) |
+                                reinterpret_cast<uintptr_t>(qtb) | reinterpret_cast<uintptr_t>(x)) & 15u) != 0)
+        route = RHS_FALLBACK;
+    const qrk::TileGeom g = make_geom(p);
+    if (route == RHS_FALLBACK) {
+        if (!p->d_q_scratch && hipMalloc((void**)&p->d_q_scratch, (size_t)std::max<int64_t>(p->nnz_q, 1) * sizeof(double)) != hipSuccess) {
+            p->d_q_scratch = nullptr;
+            (void)hipGetLastError();
+            return fail(h, QRK_STATUS_ALLOC_FAILED, "qrk_bd_factorize_rhs: cannot allocate the plan's Q scratch (nnz_q doubles)");
+        }
+        if (qrk_status st = enqueue_factorize(p, tiles, p->d_q_scratch, r, perm, hc)) return st;
+        if (qtb) qrk::launch_bd_apply_qt(g, p->d_q_scratch, b, nrhs, qtb, h->stream);
+        if (x) qrk::launch_bd_solve(g, p->max_cols, p->d_q_scratch, r, perm, b, nrhs, x, h->stream);
+        QRK_HIP(h, hipGetLastError());
+        return QRK_STATUS_OK;
+    }
+    const int pivoting = p->solver == QRK_COLPIV_HOUSEHOLDER ? 1 : 0;
+    int32_t* const redo_cnt = p->d_redo + p->redo_parity;
+    int32_t* const redo_next = p->d_redo + (p->redo_parity ^ 1);
+    int32_t* const redo_ids = p->d_redo + 2;
+    if (route == RHS_THIN)
+        QRK_HIP(h, qrk::launch_bdqr_thin_rhs(p->B, p->r, p->c, pivoting, tiles, b, (int)nrhs, p->mat_rows, p->mat_cols, p->q_format, r, perm, hc,
+                                             qtb, x, h->num_cus * 32, redo_cnt, redo_ids, h->stream));
+    else {
+        QRK_HIP(h, qrk::launch_bdqr_pair4_rhs(p->B, pivoting, tiles, b, (int)nrhs, p->mat_rows, p->mat_cols, r, perm, hc, qtb, x, p->p4_wgs,
+                                              redo_cnt, redo_ids, h->stream));
+        if (x && !qrk::bdqr_pair4_rhs_solves((int)nrhs)) qrk::launch_qless_backsolve32(p->B, r, perm, nrhs, p->mat_cols, x, h->stream);
+        // (32 x 32 tiles cover their rows and columns alike: trailing identity rows of Q only exist past them)
+        if (qtb && p->mat_rows > p->sum_rows) {
+            const size_t tail = (size_t)(p->mat_rows - p->sum_rows) * sizeof(double);
+            QRK_HIP(h, hipMemcpy2DAsync(qtb + p->sum_rows, (size_t)p->mat_rows * sizeof(double), b + p->sum_rows,
+                                        (size_t)p->mat_rows * sizeof(double), tail, (size_t)nrhs, hipMemcpyDeviceToDevice, h->stream));
+        }
+    }
+    // the tiles whose decisions were not clear of rounding, again, with the reference's own operation order; the list is empty on
+    // generic data and the workgroups return at once
+    QRK_HIP(h, qrk::launch_bdqr_qless_redo(p->B, p->r, p->c, pivoting, redo_ids, redo_cnt, redo_next, tiles, b, nrhs, p->mat_rows, p->mat_cols,
+                                           p->q_format, r, perm, hc, qtb, x, 2 * h->num_cus, h->stream));
+    p->redo_parity ^= 1;
+    QRK_HIP(h, hipGetLastError());
+    return QRK_STATUS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -846,7 +912,7 @@ qrk_status qrk_bd_plan_destroy(qrk_bd_plan p)
     (void)hipFree(p->d_toff); (void)hipFree(p->d_qoff); (void)hipFree(p->d_roff); (void)hipFree(p->d_wave_ids); (void)hipFree(p->d_w64_ids);
     (void)hipFree(p->d_wg_ids); (void)hipFree(p->d_workspace);
     (void)hipFree(p->d_col_ids); (void)hipFree(p->d_col_workspace); (void)hipFree(p->d_redo); (void)hipFree(p->d_exact_ws);
-    (void)hipFree(p->d_p4_scratch);
+    (void)hipFree(p->d_p4_scratch); (void)hipFree(p->d_q_scratch);
     delete p;
     return QRK_STATUS_OK;
 }
@@ -1076,6 +1142,68 @@ qrk_status qrk_bd_solve_r(qrk_bd_plan p, const double* r_vals, const double* y, 
     if ((st = s.back(z, d_z, nrhs * p->mat_cols))) return st;
     QRK_HIP(h, hipStreamSynchronize(h->stream));
     return QRK_STATUS_OK;
+}
+
+qrk_status qrk_bd_factorize_rhs(qrk_bd_plan p, const double* tiles, const double* b, int64_t nrhs, double* r_vals, int32_t* perm,
+                                double* hcoeffs, double* qtb, double* x, qrk_memspace space)
+{
+    if (!p) return QRK_STATUS_INVALID_ARGUMENT;
+    qrk_handle h = p->h;
+    p->factorized = false;
+    if (nrhs < 0 || (!qtb && !x))
+        return fail(h, QRK_STATUS_INVALID_ARGUMENT, "qrk_bd_factorize_rhs: at least one of qtb / x must be given, nrhs >= 0");
+    if (x && p->q_format != QRK_FULL_Q)
+        return fail(h, QRK_STATUS_UNSUPPORTED,
+                    "qrk_bd_factorize_rhs: x needs the FullQ format, R is upper triangular only there (BlockDiagonalSparseQR.h:134-154)");
+    if (p->landscape) {   // BlockDiagonalSparseQR.h:509-516: m_info = InvalidInput; return
+        p->factorized = true;
+        return QRK_STATUS_OK;
+    }
+    if ((p->B > 0 && (!tiles || !r_vals || !perm)) || (nrhs > 0 && !b))
+        return fail(h, QRK_STATUS_INVALID_ARGUMENT, "qrk_bd_factorize_rhs: NULL buffer");
+    const int64_t nb = nrhs * (int64_t)p->mat_rows;
+    if (qtb && b && nb > 0 && b < qtb + nb && qtb < b + nb)
+        return fail(h, QRK_STATUS_INVALID_ARGUMENT, "qrk_bd_factorize_rhs: b and qtb overlap");
+    QRK_HIP(h, hipSetDevice(h->device));
+    qrk_status st;
+    if (space == QRK_MEM_DEVICE) {
+        if ((st = enqueue_factorize_rhs(p, tiles, b, nrhs, r_vals, perm, hcoeffs, qtb, x))) return st;
+    } else {
+        Staging s(h);
+        double *d_t, *d_b, *d_r, *d_hc = nullptr, *d_y = nullptr, *d_x = nullptr;
+        int32_t* d_p;
+        if ((st = s.in(tiles, p->tiles_len, &d_t)) || (st = s.in(b, nb, &d_b)) || (st = s.out(p->nnz_r, &d_r)) ||
+            (st = s.out((int64_t)p->mat_cols, &d_p)))
+            return st;
+        if (hcoeffs && (st = s.out((int64_t)p->mat_cols, &d_hc))) return st;
+        if (qtb && (st = s.out(nb, &d_y))) return st;
+        if (x && (st = s.out(nrhs * (int64_t)p->mat_cols, &d_x))) return st;
+        if (!d_y && !d_x && (st = s.out(1, &d_y))) return st;      // (no right-hand side: nothing is written there)
+        if ((st = enqueue_factorize_rhs(p, d_t, d_b, nrhs, d_r, d_p, d_hc, d_y, d_x))) return st;
+        if ((st = s.back(r_vals, d_r, p->nnz_r)) || (st = s.back(perm, d_p, (int64_t)p->mat_cols)) ||
+            (st = s.back(hcoeffs, d_hc, (int64_t)p->mat_cols)) || (st = s.back(qtb, d_y, nb)) ||
+            (st = s.back(x, d_x, nrhs * (int64_t)p->mat_cols)))
+            return st;
+        QRK_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    p->factorized = true;
+    return QRK_STATUS_OK;
+}
+
+const char* qrk_bd_rhs_kernel_name(qrk_bd_plan p, int64_t nrhs)
+{
+    if (!p) return "";
+    const bool piv = p->solver == QRK_COLPIV_HOUSEHOLDER;
+    switch (rhs_route(p, nrhs)) {
+    case RHS_THIN: return piv ? "qrk::thin_rhs::bdqr_thin_rhs_kernel<true, HC>" : "qrk::thin_rhs::bdqr_thin_rhs_kernel<false, HC>";
+    case RHS_PAIR4: {
+        // (third parameter: the own-norm step, as in qrk_bd_kernel_name; arrays that are not 16-byte aligned take the fallback)
+        const bool own = qrk::bdqr_pair4_own_norm(p->B, p->p4_wgs);
+        if (piv) return own ? "qrk::bdqr_pair4_rhs_kernel<true, HC, true, NR>" : "qrk::bdqr_pair4_rhs_kernel<true, HC, false, NR>";
+        return own ? "qrk::bdqr_pair4_rhs_kernel<false, HC, true, NR>" : "qrk::bdqr_pair4_rhs_kernel<false, HC, false, NR>";
+    }
+    default: return "fallback: qrk_bd_factorize + qrk_bd_apply_qt + qrk_bd_solve through the plan's Q scratch";
+    }
 }
 
 qrk_status qrk_dense_plan_create(qrk_handle h, int32_t rows, int32_t cols, qrk_block_solver solver,

@@ -49,6 +49,29 @@ int64_t bdqr_pair4_scratch_doubles(int num_wg);
 bool bdqr_pair4_own_norm(int64_t num_tiles, int num_wg);
 hipError_t launch_bdqr_pair4(int64_t num_tiles, int pivoting, const double* tiles, double* q_vals, double* r_vals, int32_t* perm,
                              double* hcoeffs, double* scratch, int num_wg, hipStream_t stream);
+// ... and its right-hand-side form (no Q): Q^T b into qtb (may be null), the top 32 entries of every tile's part of it into the tile's own
+// columns of xtop (may be null; launch_qless_backsolve32 finishes x there), flagged tiles onto the redo list.  1 <= nrhs <= 32.  With at
+// most BDQR_PAIR4_RHS_INLANE right-hand sides (bdqr_pair4_rhs_solves) they ride through phase 1 one entry per lane, there is no phase 2,
+// and xtop receives x itself
+constexpr int BDQR_PAIR4_RHS_INLANE = 2;
+bool bdqr_pair4_rhs_solves(int nrhs);
+hipError_t launch_bdqr_pair4_rhs(int64_t num_tiles, int pivoting, const double* tiles, const double* b, int nrhs, int64_t mat_rows,
+                                 int64_t mat_cols, double* r_vals, int32_t* perm, double* hcoeffs, double* qtb, double* xtop, int num_wg,
+                                 int32_t* redo_count, int32_t* redo_ids, hipStream_t stream);
+// bdqr_thin_rhs.hip: bdqr_thin.hip's batches (1 or 2 columns, rows <= 16) factorised and solved in one launch, no Q: R, permutation, tau,
+// Q^T b (qtb, may be null) and x (may be null); at most BDQR_THIN_RHS_MAX right-hand sides (looped in the lane)
+constexpr int BDQR_THIN_RHS_MAX = 4;
+bool bdqr_thin_rhs_supported(int r, int c, int64_t nrhs);
+hipError_t launch_bdqr_thin_rhs(int64_t num_tiles, int r, int c, int pivoting, const double* tiles, const double* b, int nrhs, int64_t mat_rows,
+                                int64_t mat_cols, int q_format, double* r_vals, int32_t* perm, double* hcoeffs, double* qtb, double* x,
+                                int max_blocks, int32_t* redo_count, int32_t* redo_ids, hipStream_t stream);
+// bdqr_qless.hip: the listed tiles (uniform, at most 32 x 32) again in Eigen's operation order with Q^T b and x from the Q kept in LDS;
+// x = P R^-1 y of a uniform 32 x 32 batch in place in x
+hipError_t launch_bdqr_qless_redo(int64_t num_tiles, int r, int c, int pivoting, const int32_t* ids, const int32_t* count, int32_t* next_count,
+                                  const double* tiles, const double* b, int64_t nrhs, int64_t mat_rows, int64_t mat_cols, int q_format,
+                                  double* r_vals, int32_t* perm, double* hcoeffs, double* qtb, double* x, int num_wg, hipStream_t stream);
+void launch_qless_backsolve32(int64_t num_tiles, const double* r_vals, const int32_t* perm, int64_t nrhs, int64_t mat_cols, double* x,
+                              hipStream_t stream);
 // bdqr_quad32.hip: uniform 32 x 32 batches, FOUR tiles per wavefront, two wavefronts per SIMD (num_wg: 8 per CU); direct < 0: by launch size
 int64_t bdqr_quad32_scratch_doubles(int num_wg);
 bool bdqr_quad32_preferred(int64_t num_tiles, int num_wg);

@@ -230,6 +230,7 @@ class BlockDiagonalSparseQR:
         self.m_analysisIsok = False
         self.m_factorizationIsok = False
         self._q = self._r = self._perm = self._hc = None
+        self._qless = False      # the last factorisation was factorizeAndSolve(): no Q array
         self._rowperm = None
         if mat is not None:
             self.compute(mat)
@@ -274,6 +275,7 @@ class BlockDiagonalSparseQR:
         dev = self._ctx.device
         self._ctx.use_current_stream()
         tiles = mat.device_tiles(dev)
+        self._qless = False
         self._q = torch.empty(max(self._nnz_q, 1), dtype=torch.float64, device=dev)
         self._r = torch.empty(max(self._nnz_r, 1), dtype=torch.float64, device=dev)
         self._perm = torch.empty(max(self._cols, 1), dtype=torch.int32, device=dev)
@@ -289,6 +291,58 @@ class BlockDiagonalSparseQR:
             return   # reference: m_info = InvalidInput; return (before m_isInitialized is set)
         self.m_isInitialized = True
         self.m_factorizationIsok = True
+
+    def factorizeAndSolve(self, mat: SparseBlockDiagonal, B, returnQtB: bool = False, solve: bool = True):
+        """factorize(mat) and solve(B) in one pass that never forms Q (qrk_bd_factorize_rhs): what a Levenberg-Marquardt loop
+        needs every iteration -- R, the column permutation and Q^T f (examples/ellipse_fitting.cpp:126-142).  Runs after
+        analyzePattern() and re-uses the plan like factorize().
+
+        Returns x, or (x, Q^T B) with returnQtB, or Q^T B alone with solve=False (the only form a BLOCK_DIAGONAL_Q solver
+        supports, as with solve()).  Afterwards rValues / matrixR / colsPermutation / hCoeffs / rank / info / solveR work;
+        qValues / matrixQ / applyQ / applyQt / solve raise until the next factorize() or compute()."""
+        assert self.m_analysisIsok, "analyzePattern() should be called first"
+        assert solve or returnQtB, "nothing asked for: solve=False needs returnQtB=True"
+        dev = self._ctx.device
+        self._ctx.use_current_stream()
+        tiles = mat.device_tiles(dev)
+        b, was_np, shape = self._rhs(B, self._rows)
+        self._q, self._qless = None, True
+        self.m_isInitialized = False
+        self.m_factorizationIsok = False
+        self._r = torch.empty(max(self._nnz_r, 1), dtype=torch.float64, device=dev)
+        self._perm = torch.empty(max(self._cols, 1), dtype=torch.int32, device=dev)
+        self._hc = torch.empty(max(self._cols, 1), dtype=torch.float64, device=dev) if self._want_hc else None
+        x = torch.empty((b.shape[0], self._cols), dtype=torch.float64, device=dev) if solve else None
+        y = torch.empty_like(b) if returnQtB else None
+        capi.check(capi.lib().qrk_bd_factorize_rhs(self._plan, tiles.data_ptr(), b.data_ptr(), b.shape[0], self._r.data_ptr(),
+                                                   self._perm.data_ptr(), self._hc.data_ptr() if self._want_hc else None,
+                                                   y.data_ptr() if returnQtB else None, x.data_ptr() if solve else None,
+                                                   capi.MEM_DEVICE), self._ctx.handle)
+        info, rank = C.c_int(), C.c_int64()
+        capi.check(capi.lib().qrk_bd_info(self._plan, C.byref(info), C.byref(rank)), self._ctx.handle)
+        self.m_info, self.m_nonzeropivots = info.value, rank.value
+        if self.m_info != capi.INFO_SUCCESS:
+            return None   # (InvalidInput: nothing was computed, as in factorize())
+        self.m_isInitialized = True
+        self.m_factorizationIsok = True
+        xo = self._out(x, was_np, shape, self._cols) if solve else None
+        yo = self._out(y, was_np, shape, self._rows) if returnQtB else None
+        return (xo, yo) if (solve and returnQtB) else (xo if solve else yo)
+
+    def computeAndSolve(self, mat: SparseBlockDiagonal, B, rowPerm=None, returnQtB: bool = False, solve: bool = True):
+        """analyzePattern() + factorizeAndSolve(): compute() followed by solve(B), without Q."""
+        self.analyzePattern(mat, rowPerm)
+        return self.factorizeAndSolve(mat, B, returnQtB=returnQtB, solve=solve)
+
+    def rhsKernelName(self, nrhs: int = 1) -> str:
+        """The kernel factorizeAndSolve() runs on this plan for nrhs right-hand sides (qrk_bd_rhs_kernel_name); contains
+        'fallback' when the plan goes through an explicit Q scratch."""
+        assert self.m_analysisIsok, "analyzePattern() should be called first"
+        return capi.lib().qrk_bd_rhs_kernel_name(self._plan, int(nrhs)).decode()
+
+    def _need_q(self, what: str):
+        if self._q is None and self._qless:
+            raise RuntimeError(f"{what}: factorised without Q (factorizeAndSolve); call factorize() or compute() for the explicit Q")
 
     def rows(self) -> int:
         return self._rows
@@ -333,6 +387,7 @@ class BlockDiagonalSparseQR:
         """Explicit sparse Q, RowMajor (scipy CSR), returned by value like the reference (:235-237)."""
         import scipy.sparse as sp
         assert self.m_isInitialized
+        self._need_q("matrixQ()")
         qp, qi, _, _ = self.pattern()
         return sp.csr_matrix((self._q[:self._nnz_q].cpu().numpy(), qi, qp), shape=(self._rows, self._rows))
 
@@ -345,6 +400,7 @@ class BlockDiagonalSparseQR:
 
     # device-resident value arrays (CSR order of Q, CSC order of R, tau)
     def qValues(self) -> torch.Tensor:
+        self._need_q("qValues()")
         return self._q[:self._nnz_q]
 
     def rValues(self) -> torch.Tensor:
@@ -357,6 +413,7 @@ class BlockDiagonalSparseQR:
     def applyQt(self, B):
         """matrixQ().transpose() * B (BlockDiagonalSparseQR.h:266; test-qrkit.cpp:187)."""
         assert self.m_isInitialized
+        self._need_q("applyQt()")
         b, was_np, shape = self._rhs(B, self._rows)
         y = torch.empty_like(b)
         self._ctx.use_current_stream()
@@ -367,6 +424,7 @@ class BlockDiagonalSparseQR:
     def applyQ(self, B):
         """matrixQ() * B: the product with the explicit m_Q (:235-237) on the device (qrk_bd_apply_q)."""
         assert self.m_isInitialized
+        self._need_q("applyQ()")
         b, was_np, shape = self._rhs(B, self._rows)
         y = torch.empty_like(b)
         self._ctx.use_current_stream()
@@ -377,6 +435,7 @@ class BlockDiagonalSparseQR:
     def solve(self, B):
         """_solve_impl, BlockDiagonalSparseQR.h:257-299."""
         assert self.m_isInitialized, "The factorization should be called first, use compute()"
+        self._need_q("solve()")
         b, was_np, shape = self._rhs(B, self._rows)
         x = torch.empty((b.shape[0], self._cols), dtype=torch.float64, device=self._ctx.device)
         self._ctx.use_current_stream()
