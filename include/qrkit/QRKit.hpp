@@ -405,6 +405,44 @@ class BlockDiagonalSparseQR {
         analyzePattern(mat, rowPerm);
         return factorizeAndSolve(mat, B, QtB);
     }
+    // factorize(mat) and Q^T C for a strided DEVICE panel in one pass (qrk_bd_factorize_apply_qt): column j of C at d_C + j ldc, Q^T of
+    // it at d_out + j ldq, ldc and ldq >= rows(), the two spans disjoint.  The left half of BlockAngularSparseQR::factorize
+    // (BlockAngularSparseQR.h:459-514); uniform blocks with 1 or 2 columns and at most 16 rows never form Q.  Runs after
+    // analyzePattern(); returns when the result is in memory.  The state afterwards is that of factorizeAndSolve().
+    void factorizeApplyQtDevice(const MatrixType& mat, const double* d_C, int64_t ldc, int64_t ncols, double* d_out, int64_t ldq) {
+        assert(m_analysisIsok && "analyzePattern() should be called first");
+        int64_t tl, nq, nr;
+        check(qrk_bd_plan_sizes(m_plan, &tl, &nq, &nr));
+        const Index rows = mat.rows(), cols = mat.cols();
+        m_nq = nq; m_nr = nr;
+        m_Q.resize(rows, rows);
+        m_R.resize(rows, cols);
+        m_Qsynced = m_Rsynced = false;
+        m_isInitialized = m_factorizationIsok = false;
+        m_qless = true;
+        m_outputPerm_c.setIdentity(cols);
+        reserve(m_dtiles, m_ctiles, tl * (int64_t)sizeof(double));
+        reserve(m_dr, m_cr, nr * (int64_t)sizeof(double));
+        reserve(m_dperm, m_cperm, cols * (int64_t)sizeof(int32_t));
+        check(qrk_memcpy(m_handle, m_dtiles, mat.tiles().data(), tl * (int64_t)sizeof(double), 0));
+        check(qrk_bd_factorize_apply_qt(m_plan, (const double*)m_dtiles, d_C, ldc, ncols, (double*)m_dr, (int32_t*)m_dperm, 0, d_out, ldq,
+                                        QRK_MEM_DEVICE));
+        qrk_info info; int64_t rank;
+        check(qrk_bd_info(m_plan, &info, &rank));
+        m_info = (ComputationInfo)info;
+        if (m_info != Success) return;     // InvalidInput: nothing was written, as in factorize()
+        check(qrk_memcpy(m_handle, m_outputPerm_c.indices().data(), m_dperm, cols * (int64_t)sizeof(int32_t), 1));   // (waits for the stream)
+        m_nonzeropivots = rank;
+        m_isInitialized = true;
+        m_factorizationIsok = true;
+    }
+    // the kernel factorizeApplyQtDevice() runs on this plan for a panel of ncols columns; contains "fallback" on the explicit-Q route
+    std::string panelKernelName(int64_t ncols = 1) const {
+        assert(m_analysisIsok && "analyzePattern() should be called first");
+        return std::string(qrk_bd_panel_kernel_name(m_plan, ncols));
+    }
+    // the row permutation analyzePattern() set (rowsPermutation() before any factorisation)
+    const PermutationType& analysedRowsPermutation() const { return m_rowPerm; }
     bool hasQ() const { return !m_qless; }
 
     Index rows() const { return m_R.rows(); }
@@ -1012,14 +1050,14 @@ class BandedStripsSparseQR {
 // with Q and the triangular solve move only their vectors.  Shared by the thin solvers and the angular right block.
 class DenseDeviceQR {
   public:
-    DenseDeviceQR() : m_h(0), m_plan(0), m_dqr(0), m_dhc(0), m_dperm(0), m_rows(0), m_cols(0), m_solver(-1) {}
+    DenseDeviceQR() : m_h(0), m_plan(0), m_dqr(0), m_dhc(0), m_dperm(0), m_rows(0), m_cols(0), m_solver(-1), m_lda(0), m_owned(true) {}
     ~DenseDeviceQR() { release(); }
     DenseDeviceQR(const DenseDeviceQR&) = delete;
     DenseDeviceQR& operator=(const DenseDeviceQR&) = delete;
     // a: in the matrix, out the packed QR (R above the diagonal, essential parts below); hc: tau; perm: column permutation
     void factorize(qrk_handle h, Matrix& a, int solver, std::vector<double>& hc, std::vector<int32_t>& perm) {
         release();
-        m_h = h; m_rows = a.rows(); m_cols = a.cols(); m_solver = solver;
+        m_h = h; m_rows = a.rows(); m_cols = a.cols(); m_solver = solver; m_lda = m_rows; m_owned = true;
         const Index k = std::min(m_rows, m_cols);
         check(qrk_dense_plan_create(m_h, (int32_t)m_rows, (int32_t)m_cols, (qrk_block_solver)solver, &m_plan));
         hc.assign((size_t)std::max<Index>(k, 1), 0.0);
@@ -1040,12 +1078,22 @@ class DenseDeviceQR {
     // the same for a matrix that is already on the device (rows x cols, leading dimension rows): the buffer becomes the solver's own
     // (freed by release()); only tau and the permutation travel to the host
     void factorizeDevice(qrk_handle h, void* d_a, Index rows, Index cols, int solver, std::vector<double>& hc, std::vector<int32_t>& perm) {
+        factorizeDeviceLd(h, d_a, rows, rows, cols, solver, hc, perm, true);
+    }
+    // ... and for a WINDOW of a device matrix (rows x cols at d_a, leading dimension lda >= rows) that stays the caller's: factorised in
+    // place, never freed here; it must outlive the products and solves that follow
+    void factorizeDeviceView(qrk_handle h, double* d_a, Index lda, Index rows, Index cols, int solver, std::vector<double>& hc,
+                             std::vector<int32_t>& perm) {
+        factorizeDeviceLd(h, d_a, lda, rows, cols, solver, hc, perm, false);
+    }
+    void factorizeDeviceLd(qrk_handle h, void* d_a, Index lda, Index rows, Index cols, int solver, std::vector<double>& hc,
+                           std::vector<int32_t>& perm, bool own) {
         // (the plan - workspaces of the size of the matrix, streams, events - and the small buffers are kept from one factorisation
         //  to the next when the shape is the same: an LM loop calls compute() with one shape)
         const bool same = m_plan && m_h == h && m_rows == rows && m_cols == cols && m_solver == solver;
-        if (same) { if (m_dqr) qrk_device_free(m_h, m_dqr); }
+        if (same) { if (m_dqr && m_owned) qrk_device_free(m_h, m_dqr); m_dqr = 0; }
         else release();
-        m_h = h; m_rows = rows; m_cols = cols; m_dqr = d_a; m_solver = solver;
+        m_h = h; m_rows = rows; m_cols = cols; m_dqr = d_a; m_solver = solver; m_lda = lda; m_owned = own;
         const Index k = std::min(m_rows, m_cols);
         hc.assign((size_t)std::max<Index>(k, 1), 0.0);
         perm.assign((size_t)std::max<Index>(m_cols, 1), 0);
@@ -1054,44 +1102,45 @@ class DenseDeviceQR {
             check(qrk_device_alloc(m_h, (int64_t)(hc.size() * sizeof(double)), &m_dhc));
             check(qrk_device_alloc(m_h, (int64_t)(perm.size() * sizeof(int32_t)), &m_dperm));
         }
-        qrk_status st = qrk_dense_factorize(m_plan, (double*)m_dqr, m_rows, (double*)m_dhc, (int32_t*)m_dperm, QRK_MEM_DEVICE);
+        qrk_status st = qrk_dense_factorize(m_plan, (double*)m_dqr, m_lda, (double*)m_dhc, (int32_t*)m_dperm, QRK_MEM_DEVICE);
         if (st == QRK_STATUS_OK) st = qrk_memcpy(m_h, hc.data(), m_dhc, (int64_t)(hc.size() * sizeof(double)), 1);
         if (st == QRK_STATUS_OK) st = qrk_memcpy(m_h, perm.data(), m_dperm, (int64_t)(perm.size() * sizeof(int32_t)), 1);
         check(st);
     }
     // a device buffer for a rows x cols matrix to hand to factorizeDevice: the one of the last factorisation when the shape is the same
     void* acquireBuffer(qrk_handle h, Index rows, Index cols) {
-        if (m_dqr && m_h == h && m_rows == rows && m_cols == cols) { void* p = m_dqr; m_dqr = 0; return p; }
+        if (m_dqr && m_owned && m_h == h && m_rows == rows && m_cols == cols) { void* p = m_dqr; m_dqr = 0; return p; }
         void* p = 0;
         if (qrk_device_alloc(h, std::max<int64_t>((int64_t)rows * cols * (int64_t)sizeof(double), 8), &p) != QRK_STATUS_OK)
             throw std::runtime_error(std::string("qrkit: ") + qrk_last_error(h));
         return p;
     }
     const double* packedDevice() const { return (const double*)m_dqr; }      // R in the upper triangle of its first cols rows
+    Index leadingDim() const { return m_lda; }                                // ... with this leading dimension
     const int32_t* permDevice() const { return (const int32_t*)m_dperm; }     // (after factorizeDevice)
     void applyQDevice(double* d_v, Index nrhs, bool transpose) const {
-        check(qrk_dense_apply_q(m_plan, (const double*)m_dqr, m_rows, (const double*)m_dhc, transpose ? 1 : 0, d_v, m_rows, nrhs, QRK_MEM_DEVICE));
+        check(qrk_dense_apply_q(m_plan, (const double*)m_dqr, m_lda, (const double*)m_dhc, transpose ? 1 : 0, d_v, m_rows, nrhs, QRK_MEM_DEVICE));
         check(qrk_synchronize(m_h));
     }
     void solveRDevice(double* d_z, Index ldb, Index nrhs) const {
-        check(qrk_dense_solve_r(m_plan, (const double*)m_dqr, m_rows, d_z, ldb, nrhs, QRK_MEM_DEVICE));
+        check(qrk_dense_solve_r(m_plan, (const double*)m_dqr, m_lda, d_z, ldb, nrhs, QRK_MEM_DEVICE));
         check(qrk_synchronize(m_h));
     }
     // v (rows x nrhs, column-major) <- Q^T v or Q v
     void applyQ(Vector& v, Index nrhs, bool transpose) const {
         Scoped d(*this, v);
-        check(qrk_dense_apply_q(m_plan, (const double*)m_dqr, m_rows, (const double*)m_dhc, transpose ? 1 : 0, d.ptr(), m_rows, nrhs, QRK_MEM_DEVICE));
+        check(qrk_dense_apply_q(m_plan, (const double*)m_dqr, m_lda, (const double*)m_dhc, transpose ? 1 : 0, d.ptr(), m_rows, nrhs, QRK_MEM_DEVICE));
         d.download(v);
     }
     // z (ldb x nrhs; the first cols rows of every column) <- R^-1 z
     void solveR(Vector& z, Index ldb, Index nrhs) const {
         Scoped d(*this, z);
-        check(qrk_dense_solve_r(m_plan, (const double*)m_dqr, m_rows, d.ptr(), ldb, nrhs, QRK_MEM_DEVICE));
+        check(qrk_dense_solve_r(m_plan, (const double*)m_dqr, m_lda, d.ptr(), ldb, nrhs, QRK_MEM_DEVICE));
         d.download(z);
     }
     bool ready() const { return m_plan != 0; }
     void release() {             // (before the handle it was created with is destroyed)
-        if (m_dqr) qrk_device_free(m_h, m_dqr);
+        if (m_dqr && m_owned) qrk_device_free(m_h, m_dqr);
         if (m_dhc) qrk_device_free(m_h, m_dhc);
         if (m_dperm) qrk_device_free(m_h, m_dperm);
         if (m_plan) qrk_dense_plan_destroy(m_plan);
@@ -1118,6 +1167,8 @@ class DenseDeviceQR {
     void* m_dqr; void* m_dhc; void* m_dperm;
     Index m_rows, m_cols;
     int m_solver;
+    Index m_lda;        // leading dimension of the packed QR at m_dqr
+    bool m_owned;       // m_dqr is this solver's to free (false: a window of the caller's matrix, factorizeDeviceView)
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -1385,6 +1436,8 @@ class BlockAngularSparseQR {
         if (m_dS) qrk_device_free(m_handle, m_dS);
         if (m_dTop.p) qrk_device_free(m_handle, m_dTop.p);
         if (m_dT.p) qrk_device_free(m_handle, m_dT.p);
+        if (m_dW.p) qrk_device_free(m_handle, m_dW.p);
+        if (m_dWin.p) qrk_device_free(m_handle, m_dWin.p);
         if (m_handle) qrk_destroy(m_handle);
     }
     BlockAngularSparseQR(const BlockAngularSparseQR&) = delete;
@@ -1461,23 +1514,92 @@ class BlockAngularSparseQR {
         release();
     }
 
+    // factorize(mat) and solve(b) for ONE right-hand side in one pass that never owns Q1: the Levenberg-Marquardt step of
+    // examples/ellipse_fitting.cpp:117-142 (BlockAngularSparseQR.h:361-369, 459-514, 202-227), for a LeftSolver with
+    // factorizeApplyQtDevice() (BlockDiagonalSparseQR).  One device matrix W (rows x (m2 + 1), leading dimension rows) carries the
+    // step: the panel [J2.top(n1) | b.top(n1)] goes through qrk_bd_factorize_apply_qt into W's top n1 rows, the rows below are copied,
+    // the right solver factorizes W(m1:, 0:m2) in place, its Q^T updates rows m1.. of the last column, and the back substitution reads
+    // the strip S = W(0:m1, 0:m2) where it lies: no Q1 array, no second n1 x m2 work matrix, no copies that cut S and the bottom block
+    // out.  Returns x and, when asked, Q^T b in *QtB.  Afterwards matrixR() / colsPermutation() / rowsPermutation() / rank() / info()
+    // work; matrixQ() / applyQ() / applyQt() / solve() throw ("factorised without Q") until the next compute().
+    // With fewer bottom rows than right columns (rows - m1 < m2) the call takes the compute() + solve() route.
+    template <typename LeftMat>
+    Vector factorizeAndSolve(const BlockMatrix1x2<LeftMat, Matrix>& mat, const Vector& b, Vector* QtB = 0) {
+        const Matrix& J2in = mat.rightBlock();
+        if (m_rows - mat.leftBlock().cols() < J2in.cols()) return explicitStep(mat, b, QtB);
+        const int64_t D = (int64_t)sizeof(double);
+        return fusedStep(mat.leftBlock(), J2in.cols(), b, QtB,
+            [&](double* dWin, const std::vector<int>& rp, bool identity) {            // every row of J2, row r < n1 -> rp[r]
+                if (identity) {
+                    check(qrk_memcpy(m_handle, dWin, J2in.data(), m_rows * m_m2 * D, 0));
+                } else {
+                    Vector all((size_t)(m_rows * m_m2));
+                    for (Index c = 0; c < m_m2; ++c)
+                        for (Index r = 0; r < m_rows; ++r) all[(size_t)(c * m_rows + (r < m_n1 ? rp[(size_t)r] : (int)r))] = J2in(r, c);
+                    check(qrk_memcpy(m_handle, dWin, all.data(), m_rows * m_m2 * D, 0));
+                }
+            });
+    }
+    template <typename LeftMat, bool RM>
+    Vector factorizeAndSolve(const BlockMatrix1x2<LeftMat, SparseMatrix<RM> >& mat, const Vector& b, Vector* QtB = 0) {
+        const SparseMatrix<RM>& J2in = mat.rightBlock();
+        if (m_rows - mat.leftBlock().cols() < J2in.cols()) return explicitStep(mat, b, QtB);
+        const int64_t nnz = J2in.nonZeros(), no = J2in.outerSize();
+        void *dOuter = 0, *dInner = 0, *dVal = 0, *dMap = 0;
+        auto release = [&]() { qrk_device_free(m_handle, dOuter); qrk_device_free(m_handle, dInner); qrk_device_free(m_handle, dVal); qrk_device_free(m_handle, dMap); };
+        Vector x;
+        try {
+            check(qrk_device_alloc(m_handle, (no + 1) * 4, &dOuter));
+            check(qrk_device_alloc(m_handle, std::max<int64_t>(nnz, 1) * 4, &dInner));
+            check(qrk_device_alloc(m_handle, std::max<int64_t>(nnz, 1) * 8, &dVal));
+            check(qrk_memcpy(m_handle, dOuter, J2in.outerIndex().data(), (no + 1) * 4, 0));
+            if (nnz > 0) {
+                check(qrk_memcpy(m_handle, dInner, J2in.innerIndex().data(), nnz * 4, 0));
+                check(qrk_memcpy(m_handle, dVal, J2in.values().data(), nnz * 8, 0));
+            }
+            x = fusedStep(mat.leftBlock(), J2in.cols(), b, QtB,
+                [&](double* dWin, const std::vector<int>& rp, bool identity) {        // (qrk_sparse_window_to_dense writes W's input)
+                    if (!identity) {
+                        check(qrk_device_alloc(m_handle, std::max<int64_t>(m_n1, 1) * 4, &dMap));
+                        check(qrk_memcpy(m_handle, dMap, rp.data(), m_n1 * 4, 0));
+                    }
+                    check(qrk_sparse_window_to_dense(m_handle, RM ? 1 : 0, m_rows, m_m2, (const int32_t*)dOuter, (const int32_t*)dInner,
+                                                     (const double*)dVal, 0, m_n1, (const int32_t*)dMap, dWin, m_rows));
+                    if (m_rows > m_n1)
+                        check(qrk_sparse_window_to_dense(m_handle, RM ? 1 : 0, m_rows, m_m2, (const int32_t*)dOuter, (const int32_t*)dInner,
+                                                         (const double*)dVal, m_n1, m_rows - m_n1, 0, dWin + m_n1, m_rows));
+                });
+            check(qrk_synchronize(m_handle));
+        } catch (...) { release(); throw; }
+        release();
+        return x;
+    }
+    // analyzePattern() + factorizeAndSolve(): compute() followed by solve(b), without Q1
+    template <typename LeftMat, typename RightMat>
+    Vector computeAndSolve(const BlockMatrix1x2<LeftMat, RightMat>& mat, const Vector& b, Vector* QtB = 0) {
+        analyzePattern(mat);
+        return factorizeAndSolve(mat, b, QtB);
+    }
+    bool hasQ() const { return !m_qless; }
+
     Index rows() const { return m_rows; }
     Index cols() const { return m_cols; }
     Index rank() const { assert(m_isInitialized); return m_nonzeropivots; }
     ComputationInfo info() const { return m_info; }
     const MatrixRType& matrixR() const { if (!m_Rbuilt) makeR(); return m_R; }   // (host copy assembled on first use)
-    MatrixQType matrixQ() const { return MatrixQType(*this, false); }
+    MatrixQType matrixQ() const { needQ("matrixQ()"); return MatrixQType(*this, false); }
     const PermutationType& colsPermutation() const { return m_outputPerm_c; }
     const PermutationType& rowsPermutation() const { return m_rowPerm; }
     const LeftSolver& leftSolver() const { return m_leftSolver; }
 
     // matrixQ().transpose() * v (:607-625): rows [0,n1) <- Q1^T, then rows [m1, rows) <- Q2^T; the vector crosses PCIe once each way
-    Vector applyQt(const Vector& v) const { return applyAny(v, true); }
+    Vector applyQt(const Vector& v) const { needQ("applyQt()"); return applyAny(v, true); }
     // matrixQ() * v (:627-645): the same two factors in the opposite order
-    Vector applyQ(const Vector& v) const { return applyAny(v, false); }
+    Vector applyQ(const Vector& v) const { needQ("applyQ()"); return applyAny(v, false); }
     // _solve_impl (:202-227): x = P [R(0:rank,0:rank)^-1 (Q^T b)(0:rank)], b already row-permuted
     Vector solve(const Vector& b) const {
         assert(m_isInitialized && "The factorization should be called first, use compute()");
+        needQ("solve()");
         if (m_rows - m_m1 < m_m2) return m_outputPerm_c * solveUpperCsc(matrixR(), m_cols, applyQt(b));   // (fewer bottom rows than right columns)
         // R = [R1 S; 0 R2], block by block and on the device: y = Q^T b, z2 = R2^-1 y2 (qrk_dense_solve_r), y1 -= S(:, P2) z2
         // (qrk_dense_gemv_sub), z1 = R1^-1 y1 (the left solver's triangular step); only b and x cross PCIe
@@ -1487,7 +1609,7 @@ class BlockAngularSparseQR {
         applyDevice(y.ptr(), 1, true);
         check(qrk_memcpy_2d(m_handle, z2.p, m_m2 * D, y.ptr() + m_m1, m_m2 * D, m_m2 * D, 1, 2));
         m_dense.solveRDevice(z2.ptr(), m_m2, 1);
-        check(qrk_dense_gemv_sub(m_handle, (const double*)m_dS, m_m1, m_m1, m_m2, m_dense.permDevice(), z2.ptr(), y.ptr()));
+        check(qrk_dense_gemv_sub(m_handle, m_strip, m_stripLd, m_m1, m_m2, m_dense.permDevice(), z2.ptr(), y.ptr()));
         check(qrk_synchronize(m_handle));
         m_leftSolver.solveRDevice(y.ptr(), 1, z1.ptr());
         Vector z((size_t)(m_m1 + m_m2));
@@ -1504,7 +1626,7 @@ class BlockAngularSparseQR {
     template <typename LeftMat, typename TopFn, typename BottomFn>
     void factorizeWith(const LeftMat& left, Index m2, TopFn top, BottomFn bottom) {
         m_m1 = left.cols(); m_n1 = left.rows(); m_m2 = m2;
-        m_isInitialized = false; m_Rbuilt = false;
+        m_isInitialized = false; m_Rbuilt = false; m_qless = false;
         // J1 = Q1 R1 (:472-475)
         m_leftSolver.compute(left);
         m_info = m_leftSolver.info();
@@ -1533,6 +1655,7 @@ class BlockAngularSparseQR {
             if (st == QRK_STATUS_OK && !m_dS) { st = qrk_device_alloc(m_handle, std::max<int64_t>(m_m1 * m_m2 * D, 8), &m_dS); m_dScount = m_m1 * m_m2; }
             if (st == QRK_STATUS_OK) st = qrk_memcpy_2d(m_handle, m_dS, m_m1 * D, dT.ptr(), m_n1 * D, m_m1 * D, m_m2, 2);
             if (st != QRK_STATUS_OK) { qrk_device_free(m_handle, dBottom); check(st); }
+            m_strip = (const double*)m_dS; m_stripLd = m_m1;
         }
         m_k2 = std::min(rb, m_m2);
         std::vector<int32_t> p2;
@@ -1544,6 +1667,68 @@ class BlockAngularSparseQR {
         m_P2.assign(p2.begin(), p2.begin() + m_m2);
         m_nonzeropivots = m_leftSolver.rank() + m_k2;
         m_isInitialized = true;
+    }
+    // the fused step (factorizeAndSolve): `fill(dWin, rp, identity)` puts every row of J2 into the first m2 columns of W's input
+    // (rows x (m2 + 1), leading dimension rows; source row r < n1 at row rp[r]); b is its last column
+    template <typename LeftMat, typename FillFn>
+    Vector fusedStep(const LeftMat& left, Index m2, const Vector& b, Vector* QtB, FillFn fill) {
+        assert((Index)b.size() == m_rows && "SparseQR::solve() : invalid number of rows in the right hand side matrix");
+        m_m1 = left.cols(); m_n1 = left.rows(); m_m2 = m2;
+        m_isInitialized = false; m_Rbuilt = false; m_qless = true;
+        const int64_t D = (int64_t)sizeof(double);
+        const Index rb = m_rows - m_m1;
+        m_leftSolver.analyzePattern(left);
+        const std::vector<int>& rp = m_leftSolver.analysedRowsPermutation().indices();
+        bool identity = true;
+        for (Index r = 0; r < m_n1 && identity; ++r) identity = rp[(size_t)r] == (int)r;
+        for (Index r = 0; r < m_n1; ++r) m_rowPerm.indices()[(size_t)r] = rp[(size_t)r];
+        m_dW.reserve(*this, m_rows * (m2 + 1)); m_dWin.reserve(*this, m_rows * (m2 + 1));
+        double *W = m_dW.ptr(), *Win = m_dWin.ptr();
+        fill(Win, rp, identity);
+        check(qrk_memcpy(m_handle, Win + m2 * m_rows, b.data(), m_rows * D, 0));
+        check(qrk_synchronize(m_handle));                 // (the left solver runs on its own handle)
+        // J1 = Q1 R1 and [J2.top(n1) | b.top(n1)] <- Q1^T of it (:472-475, solveRightBlock :361-369), straight into W
+        m_leftSolver.factorizeApplyQtDevice(left, Win, m_rows, m2 + 1, W, m_rows);
+        m_info = m_leftSolver.info();
+        if (m_info != Success) return Vector();
+        if (m_rows > m_n1) check(qrk_memcpy_2d(m_handle, W + m_n1, m_rows * D, Win + m_n1, m_rows * D, (m_rows - m_n1) * D, m2 + 1, 2));
+        // rightSolver.compute(J2.bottomRows(rows - m1)) in place in W, then Q2^T on rows m1.. of the right-hand side
+        m_k2 = std::min(rb, m_m2);
+        std::vector<int32_t> p2;
+        m_dense.factorizeDeviceView(m_handle, W + m_m1, m_rows, rb, m_m2, RightSolverTag::kSolver, m_hc, p2);
+        m_dense.applyQDevice(W + m2 * m_rows + m_m1, 1, true);
+        m_strip = W; m_stripLd = m_rows;
+        // column permutation (:498-503) and rank (:510)
+        m_outputPerm_c.setIdentity(m_cols);
+        for (Index j = 0; j < m_m1; ++j) m_outputPerm_c.indices()[(size_t)j] = m_leftSolver.colsPermutation().indices()[(size_t)j];
+        for (Index j = 0; j < m_m2; ++j) m_outputPerm_c.indices()[(size_t)(m_m1 + j)] = (int)(m_m1 + p2[(size_t)j]);
+        m_P2.assign(p2.begin(), p2.begin() + m_m2);
+        m_nonzeropivots = m_leftSolver.rank() + m_k2;
+        m_isInitialized = true;
+        // _solve_impl (:202-227) on y = Q^T b = W(:, m2): z2 = R2^-1 y2, y1 -= S(:, P2) z2, z1 = R1^-1 y1
+        const double* y = W + m2 * m_rows;
+        if (QtB) { QtB->assign((size_t)m_rows, 0.0); check(qrk_memcpy(m_handle, QtB->data(), y, m_rows * D, 1)); }
+        DBuf z2(*this, m_m2), y1(*this, m_m1), z1(*this, m_m1);
+        check(qrk_memcpy_2d(m_handle, z2.p, m_m2 * D, y + m_m1, m_m2 * D, m_m2 * D, 1, 2));
+        check(qrk_memcpy_2d(m_handle, y1.p, m_m1 * D, y, m_m1 * D, m_m1 * D, 1, 2));
+        m_dense.solveRDevice(z2.ptr(), m_m2, 1);
+        check(qrk_dense_gemv_sub(m_handle, m_strip, m_stripLd, m_m1, m_m2, m_dense.permDevice(), z2.ptr(), y1.ptr()));
+        check(qrk_synchronize(m_handle));
+        m_leftSolver.solveRDevice(y1.ptr(), 1, z1.ptr());
+        Vector z((size_t)(m_m1 + m_m2));
+        check(qrk_memcpy(m_handle, z.data(), z1.p, m_m1 * D, 1));
+        check(qrk_memcpy(m_handle, z.data() + m_m1, z2.p, m_m2 * D, 1));
+        return m_outputPerm_c * z;
+    }
+    template <typename Mat1x2>
+    Vector explicitStep(const Mat1x2& mat, const Vector& b, Vector* QtB) {
+        factorize(mat);
+        if (QtB) *QtB = applyQt(b);
+        return solve(b);
+    }
+    // the last factorisation was factorizeAndSolve(): Q1 was never formed
+    void needQ(const char* what) const {
+        if (m_qless) throw std::runtime_error(std::string("qrkit: ") + what + ": factorised without Q (factorizeAndSolve); call factorize() or compute()");
     }
     // grow-only device buffer of doubles on this solver's handle (freed with the solver)
     struct Scratch {
@@ -1600,10 +1785,9 @@ class BlockAngularSparseQR {
     // makeR (:285-335): R = [R1(0:m1,:), (Q1^T J2)(0:m1, P2); 0, R2; 0, 0] as a host sparse matrix: the strip and R2 come from the device
     void makeR() const {
         const int64_t D = (int64_t)sizeof(double);
-        const Index rb = m_rows - m_m1;
         Vector S((size_t)(m_m1 * m_m2)), R2((size_t)(m_k2 * m_m2));
-        check(qrk_memcpy(m_handle, S.data(), m_dS, m_m1 * m_m2 * D, 1));
-        check(qrk_memcpy_2d(m_handle, R2.data(), m_k2 * D, m_dense.packedDevice(), rb * D, m_k2 * D, m_m2, 1));
+        check(qrk_memcpy_2d(m_handle, S.data(), m_m1 * D, m_strip, m_stripLd * D, m_m1 * D, m_m2, 1));
+        check(qrk_memcpy_2d(m_handle, R2.data(), m_k2 * D, m_dense.packedDevice(), m_dense.leadingDim() * D, m_k2 * D, m_m2, 1));
         std::vector<Triplet> t;
         const SparseMatrixColMajor& R1 = m_leftSolver.matrixR();
         for (Index c = 0; c < m_m1; ++c)
@@ -1630,6 +1814,10 @@ class BlockAngularSparseQR {
     void* m_dS = 0;                     // device: the strip S = (Q1^T J2)(0:m1, :), m1 x m2 (the packed QR of the rows below is m_dense's)
     int64_t m_dScount = 0;
     Scratch m_dTop, m_dT;               // device: J2.top(n1) and Q1^T of it, kept between factorisations
+    Scratch m_dW, m_dWin;               // device: W and its input of factorizeAndSolve(), rows x (m2 + 1) each, kept between calls
+    const double* m_strip = 0;          // the strip as the back substitution reads it: m_dS (leading dimension m1) or W (rows)
+    Index m_stripLd = 0;
+    bool m_qless = false;               // the last factorisation was factorizeAndSolve()
     std::vector<double> m_hc;
     std::vector<int> m_P2;
     mutable MatrixRType m_R;            // host copy of R, assembled by the first matrixR()

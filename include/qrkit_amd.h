@@ -231,6 +231,29 @@ qrk_status qrk_bd_factorize_rhs(qrk_bd_plan plan, const double* tiles, const dou
  * that contains "fallback" when the plan takes the explicit-Q route.  The pointer is static, like qrk_bd_kernel_name. */
 const char* qrk_bd_rhs_kernel_name(qrk_bd_plan plan, int64_t nrhs);
 
+/* factorize() and Q^T C for a panel C of ncols columns, Q never formed in device memory on the thin route: the left half
+ * of BlockAngularSparseQR::factorize (BlockAngularSparseQR.h:459-514), the panel being J2's top rows with the right-hand
+ * side of a Levenberg-Marquardt step as one more column.
+ *   c    [ (ncols-1)*ldc + mat_rows ]  in : column j at c + j*ldc, ldc >= mat_rows
+ *   qtc  [ (ncols-1)*ldq + mat_rows ]  out: column j at qtc + j*ldq, ldq >= mat_rows; rows in the plan's Q-format order
+ *                                           exactly as qrk_bd_apply_qt orders them (FullQ: [U.. | N.. | trailing identity
+ *                                           rows copy c]); rows mat_rows..ldq of a column are not touched.
+ *                                           The spans of c and qtc must not overlap.
+ *   r_vals, perm, hcoeffs              out: what qrk_bd_factorize writes for this plan (hcoeffs may be NULL)
+ * ncols >= 0 (0: the factors only).  qrk_bd_info afterwards as after qrk_bd_factorize; landscape plans as there.
+ * Uniform plans of tiles with 1 or 2 columns and at most 16 rows run one kernel that never forms Q, for a panel of any
+ * width (bdqr_thin_panel.hip); every other plan, and any plan under QRK_EXACT=1 or QRK_THIN=0, factorizes into the Q
+ * scratch owned by the plan (nnz_q doubles, allocated by the first such call) and applies it with qrk_bd_apply_qt's
+ * kernels striding by ldc / ldq.  QRK_MEM_DEVICE: enqueued on the handle's stream, no host synchronisation;
+ * QRK_MEM_HOST: staged like qrk_bd_factorize_rhs. */
+qrk_status qrk_bd_factorize_apply_qt(qrk_bd_plan plan, const double* tiles, const double* c, int64_t ldc, int64_t ncols,
+                                     double* r_vals, int32_t* perm, double* hcoeffs, double* qtc, int64_t ldq,
+                                     qrk_memspace space);
+
+/* Name of the kernel qrk_bd_factorize_apply_qt runs on this plan for a panel of ncols columns, or a string that contains
+ * "fallback" on the explicit-Q route.  The pointer is static, like qrk_bd_kernel_name. */
+const char* qrk_bd_panel_kernel_name(qrk_bd_plan plan, int64_t ncols);
+
 /* --------------------------------------------- dense right-block solver (angular) */
 
 /* A single dense Householder QR with implicit Q: the _BlockQRSolverRight of

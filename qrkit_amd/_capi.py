@@ -32,6 +32,7 @@ EXPORTS = (
     "qrk_bbs_plan_create", "qrk_bbs_plan_destroy", "qrk_bbs_plan_sizes", "qrk_bbs_factorize", "qrk_bbs_r_rows", "qrk_bbs_apply_q", "qrk_bbs_solve",
     "qrk_shard_ranges", "qrk_gather_r", "qrk_gather_x",
     "qrk_bd_factorize_rhs", "qrk_bd_rhs_kernel_name",
+    "qrk_bd_factorize_apply_qt", "qrk_bd_panel_kernel_name",
 )
 
 
@@ -106,6 +107,10 @@ def lib() -> C.CDLL:
     L.qrk_bd_factorize_rhs.argtypes = [vp, dp, dp, C.c_int64, dp, ip, dp, dp, dp, C.c_int]
     L.qrk_bd_rhs_kernel_name.restype = C.c_char_p
     L.qrk_bd_rhs_kernel_name.argtypes = [vp, C.c_int64]
+    L.qrk_bd_factorize_apply_qt.restype = C.c_int
+    L.qrk_bd_factorize_apply_qt.argtypes = [vp, dp, dp, C.c_int64, C.c_int64, dp, ip, dp, dp, C.c_int64, C.c_int]
+    L.qrk_bd_panel_kernel_name.restype = C.c_char_p
+    L.qrk_bd_panel_kernel_name.argtypes = [vp, C.c_int64]
     L.qrk_dense_plan_create.restype = C.c_int
     L.qrk_dense_plan_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int, C.POINTER(vp)]
     L.qrk_dense_plan_destroy.restype = C.c_int

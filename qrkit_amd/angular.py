@@ -62,6 +62,24 @@ def sparse_to_device_dense(context: Context, mat, row0: int = 0, nrows: Optional
     return out
 
 
+def _sparse_window_into(context: Context, mat, out: torch.Tensor):
+    """Every row of a scipy sparse matrix, dense, into the leading columns of the column-major device tensor `out`
+    (qrk_sparse_window_to_dense with out's leading dimension)."""
+    import scipy.sparse as sp
+    M = mat if sp.isspmatrix_csr(mat) or sp.isspmatrix_csc(mat) else sp.csc_matrix(mat)
+    if not M.has_canonical_format:
+        M = M.copy(); M.sum_duplicates()
+    rows, cols = M.shape
+    dev = context.device
+    outer = torch.from_numpy(np.ascontiguousarray(M.indptr, dtype=np.int32)).to(dev)
+    inner = torch.from_numpy(np.ascontiguousarray(M.indices, dtype=np.int32)).to(dev)
+    vals = torch.from_numpy(np.ascontiguousarray(M.data, dtype=np.float64)).to(dev)
+    context.use_current_stream()
+    capi.check(capi.lib().qrk_sparse_window_to_dense(
+        context.handle, 1 if sp.isspmatrix_csr(M) else 0, rows, cols, outer.data_ptr(), inner.data_ptr(), vals.data_ptr(),
+        0, rows, None, out.data_ptr(), _ld(out)), context.handle)
+
+
 class DenseColPivQR:
     """Dense Householder QR with implicit Q (Eigen::ColPivHouseholderQR / HouseholderQR interface)."""
 
@@ -71,10 +89,12 @@ class DenseColPivQR:
         self._shape = None
 
     def compute(self, A: torch.Tensor):
-        """A: (rows, cols) float64 torch tensor on the device in COLUMN-major storage, i.e. A.t() contiguous.
-        It is factorised in place (becomes the packed QR)."""
+        """A: (rows, cols) float64 torch tensor on the device in COLUMN-major storage, i.e. A.t() contiguous, or a window of
+        such a matrix (unit row stride, column stride = its leading dimension).  It is factorised in place (becomes the
+        packed QR)."""
         rows, cols = A.shape
-        assert A.dtype == torch.float64 and A.t().is_contiguous()
+        assert A.dtype == torch.float64
+        self._lda = _ld(A)
         if self._shape != (rows, cols):
             if self._plan:
                 capi.lib().qrk_dense_plan_destroy(self._plan)
@@ -86,7 +106,7 @@ class DenseColPivQR:
         self._hc = torch.empty(max(min(rows, cols), 1), dtype=torch.float64, device=A.device)
         self._perm = torch.empty(max(cols, 1), dtype=torch.int32, device=A.device)
         self._ctx.use_current_stream()
-        capi.check(capi.lib().qrk_dense_factorize(self._plan, A.data_ptr(), rows, self._hc.data_ptr(),
+        capi.check(capi.lib().qrk_dense_factorize(self._plan, A.data_ptr(), self._lda, self._hc.data_ptr(),
                                                   self._perm.data_ptr(), capi.MEM_DEVICE), self._ctx.handle)
         return self
 
@@ -110,10 +130,10 @@ class DenseColPivQR:
     def applyQ(self, B: torch.Tensor, transpose: bool) -> torch.Tensor:
         """B: (rows, nrhs) column-major device tensor, updated in place: B <- Q^T B or Q B."""
         rows = self._shape[0]
-        assert B.shape[0] == rows and B.t().is_contiguous()
+        assert B.shape[0] == rows
         self._ctx.use_current_stream()
-        capi.check(capi.lib().qrk_dense_apply_q(self._plan, self._qr.data_ptr(), rows, self._hc.data_ptr(),
-                                                1 if transpose else 0, B.data_ptr(), rows, B.shape[1], capi.MEM_DEVICE),
+        capi.check(capi.lib().qrk_dense_apply_q(self._plan, self._qr.data_ptr(), self._lda, self._hc.data_ptr(),
+                                                1 if transpose else 0, B.data_ptr(), _ld(B), B.shape[1], capi.MEM_DEVICE),
                    self._ctx.handle)
         return B
 
@@ -121,9 +141,9 @@ class DenseColPivQR:
         """B: (cols, nrhs) column-major device tensor, updated in place: B <- R^-1 B with the upper triangle of the
         packed QR (qrk_dense_solve_r; the column permutation is the caller's)."""
         rows, cols = self._shape
-        assert B.shape[0] == cols and B.t().is_contiguous()
+        assert B.shape[0] == cols
         self._ctx.use_current_stream()
-        capi.check(capi.lib().qrk_dense_solve_r(self._plan, self._qr.data_ptr(), rows, B.data_ptr(), cols, B.shape[1],
+        capi.check(capi.lib().qrk_dense_solve_r(self._plan, self._qr.data_ptr(), self._lda, B.data_ptr(), _ld(B), B.shape[1],
                                                 capi.MEM_DEVICE), self._ctx.handle)
         return B
 
@@ -388,6 +408,15 @@ class BlockedThinSparseQR:
             pass
 
 
+def _ld(t: torch.Tensor) -> int:
+    """Leading dimension of a 2-D device tensor in column-major storage (t.t() contiguous) or of a window of one."""
+    rows, cols = t.shape
+    assert rows <= 1 or t.stride(0) == 1, "column-major storage expected"
+    ld = int(t.stride(1)) if cols > 1 else rows
+    assert ld >= rows, "column-major storage expected"
+    return max(ld, 1)
+
+
 def _colmajor(t: torch.Tensor) -> torch.Tensor:
     """Device tensor with column-major storage and the same logical shape."""
     return t.t().contiguous().t()
@@ -403,10 +432,91 @@ class BlockAngularSparseQR:
         self.m_leftSolver = BlockDiagonalSparseQR(blockSolver=leftBlockSolver, qFormat=capi.FULL_Q, context=self._ctx)
         self.m_rightSolver = DenseColPivQR(self._ctx, rightSolver)
         self.m_isInitialized = False
+        self._qless = False          # the last factorisation was factorizeAndSolve(): Q1 was never formed
+        self._W = self._Win = None   # rows x (m2 + 1) work matrices of factorizeAndSolve(), kept between calls of one shape
 
     def compute(self, mat: BlockMatrix1x2):
         self.analyzePattern(mat)
         self.factorize(mat)
+
+    def computeAndSolve(self, mat: BlockMatrix1x2, b, returnQtB: bool = False):
+        """analyzePattern() + factorizeAndSolve(): compute() followed by solve(b), without Q1."""
+        self.analyzePattern(mat)
+        return self.factorizeAndSolve(mat, b, returnQtB=returnQtB)
+
+    def factorizeAndSolve(self, mat: BlockMatrix1x2, b, returnQtB: bool = False):
+        """factorize(mat) and solve(b) for ONE right-hand side in one pass that never owns Q1: the Levenberg-Marquardt step of
+        examples/ellipse_fitting.cpp:117-142 (BlockAngularSparseQR.h:361-369, 459-514, 202-227).  Runs after analyzePattern().
+
+        One device matrix W (rows x (m2 + 1), leading dimension rows) carries the step: the panel [J2.top(n1) | b.top(n1)]
+        goes through qrk_bd_factorize_apply_qt into W's top n1 rows, the rows below are copied, the right solver factorizes
+        W(m1:, 0:m2) in place, its Q^T updates rows m1.. of the last column, and the back substitution reads the strip
+        S = W(0:m1, 0:m2) where it lies.  Returns x, or (x, Q^T b) with returnQtB.  Afterwards matrixR / colsPermutation /
+        rowsPermutation / rank / info work; matrixQ / applyQ / applyQt / solve raise until the next compute().
+
+        With fewer bottom rows than right columns (rows - m1 < m2) the call takes the compute() + solve() route."""
+        dev = self._ctx.device
+        left, right = mat.leftBlock(), mat.rightBlock()
+        m1, n1 = self.m_leftCols, self.m_leftRows
+        rows, m2 = int(right.shape[0]), int(right.shape[1])
+        n2 = rows - n1
+        was_np = not isinstance(b, torch.Tensor)
+        bt = (torch.as_tensor(np.asarray(b, dtype=np.float64)) if was_np else b).reshape(-1)
+        assert bt.shape[0] == rows, "SparseQR::solve() : invalid number of rows in the right hand side matrix"
+        if rows - m1 < m2:
+            self.factorize(mat)
+            x = self.solve(b)
+            return (x, self.applyQt(b)) if returnQtB else x
+        if self._W is None or tuple(self._W.shape) != (rows, m2 + 1):
+            self._W = torch.empty(m2 + 1, rows, dtype=torch.float64, device=dev).t()       # column-major
+            self._Win = torch.empty(m2 + 1, rows, dtype=torch.float64, device=dev).t()
+        W, Win = self._W, self._Win
+        self._ctx.use_current_stream()
+        if hasattr(right, "tocsc"):          # sparse right block: only its nonzeros cross PCIe, made dense in W's input
+            _sparse_window_into(self._ctx, right, Win)
+        else:
+            J2 = torch.as_tensor(np.asarray(right, dtype=np.float64)) if not isinstance(right, torch.Tensor) else right
+            Win[:, :m2].copy_(J2)
+        Win[:, m2].copy_(bt)
+        self._qless = True
+        self.m_isInitialized = False
+        # J1 = Q1 R1 and [J2.top(n1) | b.top(n1)] <- Q1^T of it (:472-475, :361-369); the left solver's row permutation is the identity
+        self.m_leftSolver.analyzePattern(left)
+        self.m_leftSolver.factorizeApplyQtDevice(left, Win.data_ptr(), rows, m2 + 1, W.data_ptr(), rows)
+        assert self.m_leftSolver.info() == capi.INFO_SUCCESS
+        if n2 > 0:
+            W[n1:, :].copy_(Win[n1:, :])
+        # rightSolver.compute(J2.bottomRows(rows - m1)) in place in W, then Q2^T on rows m1.. of the right-hand side
+        self.m_rightSolver.compute(W[m1:, :m2])
+        self.m_rightSolver.applyQ(W[m1:, m2:], transpose=True)
+        self._J2 = W[:, :m2]
+        self._P2 = self.m_rightSolver.colsPermutation().long()
+        self._m1, self._m2, self._n1, self._n2 = m1, m2, n1, n2
+        p1 = torch.as_tensor(self.m_leftSolver.colsPermutation(), device=dev).long()
+        self.m_outputPerm_c = torch.cat([p1, m1 + self._P2]).to(torch.int32)
+        self.m_rowPerm = np.arange(self._rows, dtype=np.int32)
+        self.m_nonzeropivots = self.m_leftSolver.rank() + min(rows - m1, m2)
+        self.m_isInitialized = True
+        self.m_info = capi.INFO_SUCCESS
+        # _solve_impl (:202-227) on y = Q^T b = W(:, m2): z2 = R2^-1 y2, y1 -= S(:, P2) z2, z1 = R1^-1 y1
+        y = W[:, m2]
+        qtb = y.clone() if returnQtB else None
+        z2 = self.m_rightSolver.solveR(y[m1:m1 + m2].clone().reshape(m2, 1))
+        rhs1 = y[:m1].clone().reshape(m1, 1)
+        p2 = self.m_rightSolver.colsPermutation()
+        capi.check(capi.lib().qrk_dense_gemv_sub(self._ctx.handle, W.data_ptr(), rows, m1, m2, p2.data_ptr(), z2.data_ptr(),
+                                                 rhs1.data_ptr()), self._ctx.handle)
+        z1 = self.m_leftSolver.solveR(rhs1)
+        x = torch.empty(m1 + m2, dtype=torch.float64, device=dev)
+        x[self.m_outputPerm_c.long()] = torch.cat([z1.reshape(-1), z2.reshape(-1)])
+        if was_np:
+            x = x.cpu().numpy()
+            qtb = qtb.cpu().numpy() if returnQtB else None
+        return (x, qtb) if returnQtB else x
+
+    def _need_q(self, what: str):
+        if self._qless:
+            raise RuntimeError(f"{what}: factorised without Q (factorizeAndSolve); call factorize() or compute() for the explicit Q")
 
     def analyzePattern(self, mat: BlockMatrix1x2):
         """:431-449: identity permutations, left block size."""
@@ -422,6 +532,7 @@ class BlockAngularSparseQR:
         m1, n1 = self.m_leftCols, self.m_leftRows
         m2 = int(right.shape[1])
         n2 = int(right.shape[0]) - n1
+        self._qless = False
         # J1 = Q1 R1 (:472-475)
         self.m_leftSolver.compute(left)
         assert self.m_leftSolver.info() == capi.INFO_SUCCESS
@@ -481,6 +592,7 @@ class BlockAngularSparseQR:
 
     def applyQt(self, v):
         """matrixQ().transpose() * v (:607-625): top n1 rows <- Q1^T v_top, then rows m1.. <- Q2^T of them."""
+        self._need_q("applyQt()")
         was_np = not isinstance(v, torch.Tensor)
         t = torch.as_tensor(np.asarray(v, dtype=np.float64)) if was_np else v
         t = t.to(self._ctx.device, torch.float64).reshape(self._rows, -1).clone()
@@ -494,6 +606,7 @@ class BlockAngularSparseQR:
 
     def applyQ(self, v):
         """matrixQ() * v (:627-645): rows m1.. <- Q2 of them, then the top n1 rows <- Q1 of them."""
+        self._need_q("applyQ()")
         was_np = not isinstance(v, torch.Tensor)
         t = torch.as_tensor(np.asarray(v, dtype=np.float64)) if was_np else v
         t = t.to(self._ctx.device, torch.float64).reshape(self._rows, -1).clone()
@@ -508,11 +621,13 @@ class BlockAngularSparseQR:
     def matrixQ(self):
         """Product expression (BlockAngularSparseQR.h:651-701): matrixQ() @ v, .transpose() @ v, .toSparse()."""
         from .qproduct import QProduct
+        self._need_q("matrixQ()")
         return QProduct(self)
 
     def solve(self, b):
         """_solve_impl (:202-227): x = P [R(0:rank,0:rank)^-1 (Q^T b)(0:rank)] (dense back substitution on the host
         side of the mirror is avoided: the triangular solve uses the block structure on the device)."""
+        self._need_q("solve()")
         was_np = not isinstance(b, torch.Tensor)
         y = self.applyQt(torch.as_tensor(np.asarray(b, dtype=np.float64)) if was_np else b)
         y = y.reshape(self._rows, -1)

@@ -88,6 +88,10 @@ bd_q_tail_ones_kernel(double* __restrict__ q_vals, int64_t start, int64_t count)
     if (i < count) q_vals[start + i] = 1.0;
 }
 
+// leading dimensions of b and y in the Q^T kernels below (qrk_bd_factorize_apply_qt's fallback passes a strided panel; 0: mat_rows)
+__device__ __forceinline__ int64_t geom_ldb(const TileGeom& g) { return g.ldb ? g.ldb : (int64_t)g.mat_rows; }
+__device__ __forceinline__ int64_t geom_ldy(const TileGeom& g) { return g.ldy ? g.ldy : (int64_t)g.mat_rows; }
+
 // y = Q^T b for one tile and one right-hand side per wavefront (tiles with rows <= 64 use the
 // lanes as output index; larger tiles loop).  FullQ: y[base_col+k] for k < c, y[N + m1 + k - c]
 // for the N part; BlockDiagonalQ: y[base_row + k].
@@ -102,8 +106,8 @@ bd_apply_qt_kernel(TileGeom g, const double* __restrict__ q_vals, const double* 
         int r, c, base_row, base_col;
         int64_t qoff, roff;
         tile_geom(g, t, r, c, qoff, roff, base_row, base_col);
-        const double* bb = b + rhs * (int64_t)g.mat_rows + base_row;
-        double* yy = y + rhs * (int64_t)g.mat_rows;
+        const double* bb = b + rhs * geom_ldb(g) + base_row;
+        double* yy = y + rhs * geom_ldy(g);
         const int m1 = base_row - base_col;
         for (int k = lane; k < r; k += 64) {
             double s = 0.0;
@@ -135,8 +139,8 @@ bd_apply_qt_small_kernel(TileGeom g, const double* __restrict__ q_vals, const do
         const int64_t t = w % g.num_tiles, rhs = w / g.num_tiles;
         const int base_row = (int)(t * r), base_col = (int)(t * c);
         const double* q = q_vals + t * (int64_t)r * r;
-        const double* bb = b + rhs * (int64_t)g.mat_rows + base_row;
-        double* yy = y + rhs * (int64_t)g.mat_rows;
+        const double* bb = b + rhs * geom_ldb(g) + base_row;
+        double* yy = y + rhs * geom_ldy(g);
         double s = 0.0;
         {
             double qv[RP], bv[RP];                             // (every row in flight before the first use; round 5)
@@ -180,12 +184,13 @@ bd_apply_qt_small_many_kernel(TileGeom g, const double* __restrict__ q_vals, con
     if (g.q_format == 0) idx = k < c ? base_col + k : g.mat_cols + (base_row - base_col) + (k - c);
     else idx = base_row + k;
     const int64_t r0 = chunk * APQT_CHUNK, r1 = r0 + APQT_CHUNK < nrhs ? r0 + APQT_CHUNK : nrhs;
-    const double* bp = b + r0 * (int64_t)g.mat_rows + (on ? base_row + k : 0);
+    const int64_t ldb = geom_ldb(g), ldy = geom_ldy(g);
+    const double* bp = b + r0 * ldb + (on ? base_row + k : 0);
     double bn = r0 < r1 ? *bp : 0.0;
     for (int64_t rhs = r0; rhs < r1; ++rhs) {
         const int par = (int)(rhs & 1);
         sb[par][lane] = on ? bn : 0.0;
-        bp += g.mat_rows;
+        bp += ldb;
         if (rhs + 1 < r1) bn = *bp;                          // next right-hand side in flight
         __builtin_amdgcn_wave_barrier();
         double s0 = 0.0, s1 = 0.0;
@@ -194,7 +199,7 @@ bd_apply_qt_small_many_kernel(TileGeom g, const double* __restrict__ q_vals, con
             const double2 v2 = *reinterpret_cast<const double2*>(&sb[par][sub * RP + j]);
             s0 = fma(qk[j], v2.x, s0); s1 = fma(qk[j + 1], v2.y, s1);
         }
-        if (on) y[rhs * (int64_t)g.mat_rows + idx] = s0 + s1;
+        if (on) y[rhs * ldy + idx] = s0 + s1;
         __builtin_amdgcn_wave_barrier();
     }
 }
@@ -237,7 +242,7 @@ bd_copy_tail_kernel(TileGeom g, const double* __restrict__ b, int64_t nrhs, doub
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i < ntail * nrhs) {
         const int64_t rhs = i / ntail, k = i - rhs * ntail;
-        y[rhs * (int64_t)g.mat_rows + g.sum_rows + k] = b[rhs * (int64_t)g.mat_rows + g.sum_rows + k];
+        y[rhs * geom_ldy(g) + g.sum_rows + k] = b[rhs * geom_ldb(g) + g.sum_rows + k];
     }
 }
 

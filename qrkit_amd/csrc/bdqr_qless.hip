@@ -88,6 +88,68 @@ hipError_t launch_bdqr_qless_redo(int64_t num_tiles, int r, int c, int pivoting,
     return hipGetLastError();
 }
 
+// The panel sibling of bdqr_qless_redo_kernel, behind qrk_bd_factorize_apply_qt (bdqr_thin_panel.hip): the listed tiles again, then
+// Q_i^T on the tile's rows of EVERY column of a strided panel (column j at pc + j * ldc, out at qtc + j * ldq), no x.  Tiles of at most
+// 32 rows: lane k of each half of the wavefront owns output entry k, the two halves take alternate columns.
+template <bool PIVOT>
+__global__ void __launch_bounds__(64)
+bdqr_qless_redo_panel_kernel(int64_t num_tiles, int r, int c, const int32_t* __restrict__ ids, const int32_t* __restrict__ count,
+                             int32_t* next_count, const double* __restrict__ tiles, const double* __restrict__ pc, int64_t ldc,
+                             int64_t ncols, int64_t mat_cols, int q_format, double* __restrict__ r_vals, int32_t* __restrict__ perm,
+                             double* __restrict__ hcoeffs, double* __restrict__ qtc, int64_t ldq)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char qless_smem[];
+    exact::Shared sh;
+    double* W = exact::carve_shared<64>(qless_smem, r, c, sh);      // [r][c] working copy, row-major
+    double* q = W + r * c;                                          // [r][r] Q_i, row-major
+    const int lane = threadIdx.x, k = lane & 31, half = lane >> 5;
+    if (next_count && blockIdx.x == 0 && lane == 0) *next_count = 0;
+    int64_t n = (int64_t)*count;
+    if (n > num_tiles) n = num_tiles;
+    for (int64_t li = blockIdx.x; li < n; li += gridDim.x) {
+        const int64_t t = (int64_t)ids[li];
+        if (t < 0 || t >= num_tiles) continue;
+        const int cbase = (int)(t * c);
+        __syncthreads();
+        exact::tile_qr<PIVOT, 64>(r, c, tiles + t * (int64_t)r * c, W, q, sh);
+        exact::tile_store<64>(r, c, cbase, W, nullptr, sh, perm, hcoeffs, r_vals + t * (int64_t)(c * (c + 1) / 2), nullptr);
+        __syncthreads();
+        const int64_t base_row = t * (int64_t)r;
+        if (k < r) {
+            int64_t idx;
+            if (q_format == 0) idx = k < c ? (int64_t)cbase + k : mat_cols + (base_row - cbase) + (k - c);
+            else idx = base_row + k;
+            for (int64_t j = half; j < ncols; j += 2) {
+                // y_k = sum_i Q(i, k) c_i, i ascending: the sum of bd_apply_qt_kernel
+                const double* bb = pc + j * ldc + base_row;
+                double yk = 0.0;
+                for (int i = 0; i < r; ++i) yk = fma(q[i * r + k], bb[i], yk);
+                qtc[j * ldq + idx] = yk;
+            }
+        }
+    }
+}
+
+hipError_t launch_bdqr_qless_redo_panel(int64_t num_tiles, int r, int c, int pivoting, const int32_t* ids, const int32_t* count,
+                                        int32_t* next_count, const double* tiles, const double* pc, int64_t ldc, int64_t ncols,
+                                        int64_t mat_cols, int q_format, double* r_vals, int32_t* perm, double* hcoeffs, double* qtc,
+                                        int64_t ldq, int num_wg, hipStream_t stream)
+{
+    if (num_tiles <= 0 || num_wg <= 0) return hipSuccess;
+    if (r > qless::MAXD || c > r || c < 1) return hipErrorInvalidValue;
+    // (the carve of launch_bdqr_qless_redo)
+    const size_t smem = (((size_t)(r + 3 * c + 64) * sizeof(double) + (size_t)(2 * c + 64) * sizeof(int) + 15) & ~(size_t)15) + 16 +
+                        (size_t)(r * c + r * r) * sizeof(double);
+    const dim3 grid((unsigned)((int64_t)num_wg < num_tiles ? num_wg : num_tiles)), block(64);
+    if (pivoting)
+        hipLaunchKernelGGL(bdqr_qless_redo_panel_kernel<true>, grid, block, smem, stream, num_tiles, r, c, ids, count, next_count, tiles, pc,
+                           ldc, ncols, mat_cols, q_format, r_vals, perm, hcoeffs, qtc, ldq);
+    else
+        hipLaunchKernelGGL(bdqr_qless_redo_panel_kernel<false>, grid, block, smem, stream, num_tiles, r, c, ids, count, next_count, tiles, pc,
+                           ldc, ncols, mat_cols, q_format, r_vals, perm, hcoeffs, qtc, ldq);
+    return hipGetLastError();
+}
+
 __global__ void __launch_bounds__(64)
 qless_backsolve32_kernel(int64_t num_tiles, const double* __restrict__ r_vals, const int32_t* __restrict__ perm, int64_t nrhs,
                          int64_t mat_cols, double* x)

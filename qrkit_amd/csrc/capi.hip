@@ -556,6 +556,50 @@ qrk_status enqueue_factorize_rhs(qrk_bd_plan_s* p, const double* tiles, const do
     return QRK_STATUS_OK;
 }
 
+// The route of qrk_bd_factorize_apply_qt on this plan: bdqr_thin_panel.hip under the conditions that pick bdqr_thin.hip in
+// enqueue_factorize (uniform, 1 or 2 columns, at most 16 rows), for a panel of any width; every other plan through the plan's Q scratch.
+bool panel_route_thin(const qrk_bd_plan_s* p)
+{
+    const qrk_handle h = p->h;
+    if (h->force_exact || !p->uniform || p->landscape || p->B <= 0 || !p->d_redo) return false;
+    return p->max_dim <= 16 && p->r >= p->c && p->c <= 2 && h->use_small_kernel && h->use_thin_kernel && qrk::bdqr_thin_panel_supported(p->r, p->c);
+}
+
+// factorize() and Q^T C for a strided panel on the handle's stream, device pointers.  No host synchronisation (the fallback allocates the
+// plan's Q scratch on its first use); the fallback hands both leading dimensions to qrk_bd_apply_qt's kernels, which stride by them.
+qrk_status enqueue_factorize_apply_qt(qrk_bd_plan_s* p, const double* tiles, const double* c, int64_t ldc, int64_t ncols, double* r,
+                                      int32_t* perm, double* hc, double* qtc, int64_t ldq)
+{
+    qrk_handle h = p->h;
+    if (!panel_route_thin(p)) {
+        if (!p->d_q_scratch && hipMalloc((void**)&p->d_q_scratch, (size_t)std::max<int64_t>(p->nnz_q, 1) * sizeof(double)) != hipSuccess) {
+            p->d_q_scratch = nullptr;
+            (void)hipGetLastError();
+            return fail(h, QRK_STATUS_ALLOC_FAILED, "qrk_bd_factorize_apply_qt: cannot allocate the plan's Q scratch (nnz_q doubles)");
+        }
+        if (qrk_status st = enqueue_factorize(p, tiles, p->d_q_scratch, r, perm, hc)) return st;
+        if (ncols > 0) {
+            qrk::TileGeom g = make_geom(p);
+            g.ldb = ldc; g.ldy = ldq;
+            qrk::launch_bd_apply_qt(g, p->d_q_scratch, c, ncols, qtc, h->stream);
+        }
+        QRK_HIP(h, hipGetLastError());
+        return QRK_STATUS_OK;
+    }
+    const int pivoting = p->solver == QRK_COLPIV_HOUSEHOLDER ? 1 : 0;
+    int32_t* const redo_cnt = p->d_redo + p->redo_parity;
+    int32_t* const redo_next = p->d_redo + (p->redo_parity ^ 1);
+    int32_t* const redo_ids = p->d_redo + 2;
+    QRK_HIP(h, qrk::launch_bdqr_thin_panel(p->B, p->r, p->c, pivoting, tiles, c, ldc, ncols, p->mat_rows, p->mat_cols, p->q_format, r, perm, hc,
+                                           qtc, ldq, h->num_cus, redo_cnt, redo_ids, h->stream));
+    // the tiles whose decisions were not clear of rounding, again, with the reference's own operation order, for the whole panel
+    QRK_HIP(h, qrk::launch_bdqr_qless_redo_panel(p->B, p->r, p->c, pivoting, redo_ids, redo_cnt, redo_next, tiles, c, ldc, ncols, p->mat_cols,
+                                                 p->q_format, r, perm, hc, qtc, ldq, 2 * h->num_cus, h->stream));
+    p->redo_parity ^= 1;
+    QRK_HIP(h, hipGetLastError());
+    return QRK_STATUS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1204,6 +1248,63 @@ const char* qrk_bd_rhs_kernel_name(qrk_bd_plan p, int64_t nrhs)
     }
     default: return "fallback: qrk_bd_factorize + qrk_bd_apply_qt + qrk_bd_solve through the plan's Q scratch";
     }
+}
+
+qrk_status qrk_bd_factorize_apply_qt(qrk_bd_plan p, const double* tiles, const double* c, int64_t ldc, int64_t ncols, double* r_vals,
+                                     int32_t* perm, double* hcoeffs, double* qtc, int64_t ldq, qrk_memspace space)
+{
+    if (!p) return fail(nullptr, QRK_STATUS_INVALID_ARGUMENT, "qrk_bd_factorize_apply_qt: NULL plan");
+    qrk_handle h = p->h;
+    p->factorized = false;
+    if (ncols < 0) return fail(h, QRK_STATUS_INVALID_ARGUMENT, "qrk_bd_factorize_apply_qt: ncols < 0");
+    if (p->landscape) {   // BlockDiagonalSparseQR.h:509-516: m_info = InvalidInput; return
+        p->factorized = true;
+        return QRK_STATUS_OK;
+    }
+    if (ldc < p->mat_rows || ldq < p->mat_rows)
+        return fail(h, QRK_STATUS_INVALID_ARGUMENT, "qrk_bd_factorize_apply_qt: ldc and ldq must be at least the plan's rows");
+    if ((p->B > 0 && (!tiles || !r_vals || !perm)) || (ncols > 0 && p->mat_rows > 0 && (!c || !qtc)))
+        return fail(h, QRK_STATUS_INVALID_ARGUMENT, "qrk_bd_factorize_apply_qt: NULL buffer");
+    const int64_t span_c = ncols > 0 ? (ncols - 1) * ldc + p->mat_rows : 0, span_q = ncols > 0 ? (ncols - 1) * ldq + p->mat_rows : 0;
+    if (span_c > 0 && span_q > 0 && c < qtc + span_q && qtc < c + span_c)
+        return fail(h, QRK_STATUS_INVALID_ARGUMENT, "qrk_bd_factorize_apply_qt: the spans of c and qtc overlap");
+    QRK_HIP(h, hipSetDevice(h->device));
+    qrk_status st;
+    if (space == QRK_MEM_DEVICE) {
+        if ((st = enqueue_factorize_apply_qt(p, tiles, c, ldc, ncols, r_vals, perm, hcoeffs, qtc, ldq))) return st;
+    } else {
+        Staging s(h);
+        double *d_t, *d_c = nullptr, *d_r, *d_hc = nullptr, *d_y = nullptr;
+        int32_t* d_p;
+        if ((st = s.in(tiles, p->tiles_len, &d_t)) || (st = s.in(c, span_c, &d_c)) || (st = s.out(p->nnz_r, &d_r)) ||
+            (st = s.out((int64_t)p->mat_cols, &d_p)))
+            return st;
+        if (hcoeffs && (st = s.out((int64_t)p->mat_cols, &d_hc))) return st;
+        // (the padding rows of qtc between mat_rows and ldq are the caller's: they travel in and out unchanged)
+        if (span_q > 0 && (st = s.in(qtc, span_q, &d_y))) return st;
+        if ((st = enqueue_factorize_apply_qt(p, d_t, d_c, ldc, ncols, d_r, d_p, d_hc, d_y, ldq))) return st;
+        if ((st = s.back(r_vals, d_r, p->nnz_r)) || (st = s.back(perm, d_p, (int64_t)p->mat_cols)) ||
+            (st = s.back(hcoeffs, d_hc, (int64_t)p->mat_cols)) || (st = s.back(qtc, d_y, span_q)))
+            return st;
+        QRK_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    p->factorized = true;
+    return QRK_STATUS_OK;
+}
+
+const char* qrk_bd_panel_kernel_name(qrk_bd_plan p, int64_t ncols)
+{
+    if (!p) return "";
+    (void)ncols;     // (the thin route serves every width; the width only sets the grid)
+    if (panel_route_thin(p)) {
+        const bool piv = p->solver == QRK_COLPIV_HOUSEHOLDER;
+        // (<PIVOT, rows at most, columns in flight per trip>: the instantiations of launch_bdqr_thin_panel)
+        if (p->r <= 2) return piv ? "qrk::thin_panel::bdqr_thin_panel_kernel<true, 2, 4>" : "qrk::thin_panel::bdqr_thin_panel_kernel<false, 2, 4>";
+        if (p->r <= 4) return piv ? "qrk::thin_panel::bdqr_thin_panel_kernel<true, 4, 2>" : "qrk::thin_panel::bdqr_thin_panel_kernel<false, 4, 2>";
+        if (p->r <= 8) return piv ? "qrk::thin_panel::bdqr_thin_panel_kernel<true, 8, 2>" : "qrk::thin_panel::bdqr_thin_panel_kernel<false, 8, 2>";
+        return piv ? "qrk::thin_panel::bdqr_thin_panel_kernel<true, 16, 1>" : "qrk::thin_panel::bdqr_thin_panel_kernel<false, 16, 1>";
+    }
+    return "fallback: qrk_bd_factorize + qrk_bd_apply_qt through the plan's Q scratch";
 }
 
 qrk_status qrk_dense_plan_create(qrk_handle h, int32_t rows, int32_t cols, qrk_block_solver solver,

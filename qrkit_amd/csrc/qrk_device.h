@@ -40,6 +40,7 @@ struct TileGeom {
     int32_t sum_rows;            // rows covered by tiles; rows beyond get Q(i,i) = 1
     int64_t nnz_q_tiles;         // sum r^2
     int32_t q_format;            // 0 FullQ, 1 BlockDiagonalQ
+    int64_t ldb, ldy;            // launch_bd_apply_qt only: leading dimensions of b and y (0: mat_rows)
 };
 
 // ---- host-side launchers (defined next to their kernels)
@@ -70,6 +71,23 @@ hipError_t launch_bdqr_thin_rhs(int64_t num_tiles, int r, int c, int pivoting, c
 hipError_t launch_bdqr_qless_redo(int64_t num_tiles, int r, int c, int pivoting, const int32_t* ids, const int32_t* count, int32_t* next_count,
                                   const double* tiles, const double* b, int64_t nrhs, int64_t mat_rows, int64_t mat_cols, int q_format,
                                   double* r_vals, int32_t* perm, double* hcoeffs, double* qtb, double* x, int num_wg, hipStream_t stream);
+// bdqr_thin_panel.hip: the same batches factorised and Q^T applied to a panel of ncols columns (column j at pc + j * ldc, out at
+// qtc + j * ldq), no Q, no x: a 2-D grid of (chunks of 256 tiles) x (slices of cols_per_slice columns), `group` columns in flight per trip
+struct ThinPanelGrid {
+    int chunks, slices, cols_per_slice, group;
+    size_t smem;
+};
+bool bdqr_thin_panel_supported(int r, int c);
+ThinPanelGrid bdqr_thin_panel_grid(int64_t num_tiles, int r, int c, int64_t ncols, int num_cus);
+hipError_t launch_bdqr_thin_panel(int64_t num_tiles, int r, int c, int pivoting, const double* tiles, const double* pc, int64_t ldc,
+                                  int64_t ncols, int64_t mat_rows, int64_t mat_cols, int q_format, double* r_vals, int32_t* perm,
+                                  double* hcoeffs, double* qtc, int64_t ldq, int num_cus, int32_t* redo_count, int32_t* redo_ids,
+                                  hipStream_t stream);
+// ... and the redo of its flagged tiles for the whole panel (bdqr_qless.hip): both leading dimensions, no x
+hipError_t launch_bdqr_qless_redo_panel(int64_t num_tiles, int r, int c, int pivoting, const int32_t* ids, const int32_t* count,
+                                        int32_t* next_count, const double* tiles, const double* pc, int64_t ldc, int64_t ncols,
+                                        int64_t mat_cols, int q_format, double* r_vals, int32_t* perm, double* hcoeffs, double* qtc,
+                                        int64_t ldq, int num_wg, hipStream_t stream);
 void launch_qless_backsolve32(int64_t num_tiles, const double* r_vals, const int32_t* perm, int64_t nrhs, int64_t mat_cols, double* x,
                               hipStream_t stream);
 // bdqr_quad32.hip: uniform 32 x 32 batches, FOUR tiles per wavefront, two wavefronts per SIMD (num_wg: 8 per CU); direct < 0: by launch size

@@ -340,6 +340,39 @@ class BlockDiagonalSparseQR:
         assert self.m_analysisIsok, "analyzePattern() should be called first"
         return capi.lib().qrk_bd_rhs_kernel_name(self._plan, int(nrhs)).decode()
 
+    def factorizeApplyQtDevice(self, mat: SparseBlockDiagonal, C_ptr: int, ldc: int, ncols: int, out_ptr: int, ldq: int):
+        """factorize(mat) and Q^T C for a strided device panel in one pass (qrk_bd_factorize_apply_qt): column j of C at
+        C_ptr + 8 j ldc bytes, Q^T of it at out_ptr + 8 j ldq bytes, ldc, ldq >= rows(); the spans must not overlap.  The
+        left half of BlockAngularSparseQR::factorize (BlockAngularSparseQR.h:459-514); uniform plans of tiles with 1 or 2
+        columns and at most 16 rows never form Q.  Runs after analyzePattern().  The state afterwards is that of
+        factorizeAndSolve(): R, permutation, rank, info and solveR work, the Q accessors raise."""
+        assert self.m_analysisIsok, "analyzePattern() should be called first"
+        dev = self._ctx.device
+        self._ctx.use_current_stream()
+        tiles = mat.device_tiles(dev)
+        self._q, self._qless = None, True
+        self.m_isInitialized = False
+        self.m_factorizationIsok = False
+        self._r = torch.empty(max(self._nnz_r, 1), dtype=torch.float64, device=dev)
+        self._perm = torch.empty(max(self._cols, 1), dtype=torch.int32, device=dev)
+        self._hc = torch.empty(max(self._cols, 1), dtype=torch.float64, device=dev) if self._want_hc else None
+        capi.check(capi.lib().qrk_bd_factorize_apply_qt(self._plan, tiles.data_ptr(), C_ptr, int(ldc), int(ncols), self._r.data_ptr(),
+                                                        self._perm.data_ptr(), self._hc.data_ptr() if self._want_hc else None,
+                                                        out_ptr, int(ldq), capi.MEM_DEVICE), self._ctx.handle)
+        info, rank = C.c_int(), C.c_int64()
+        capi.check(capi.lib().qrk_bd_info(self._plan, C.byref(info), C.byref(rank)), self._ctx.handle)
+        self.m_info, self.m_nonzeropivots = info.value, rank.value
+        if self.m_info != capi.INFO_SUCCESS:
+            return   # (InvalidInput: nothing was computed, as in factorize())
+        self.m_isInitialized = True
+        self.m_factorizationIsok = True
+
+    def panelKernelName(self, ncols: int = 1) -> str:
+        """The kernel factorizeApplyQtDevice() runs on this plan for a panel of ncols columns (qrk_bd_panel_kernel_name);
+        contains 'fallback' when the plan goes through an explicit Q scratch."""
+        assert self.m_analysisIsok, "analyzePattern() should be called first"
+        return capi.lib().qrk_bd_panel_kernel_name(self._plan, int(ncols)).decode()
+
     def _need_q(self, what: str):
         if self._q is None and self._qless:
             raise RuntimeError(f"{what}: factorised without Q (factorizeAndSolve); call factorize() or compute() for the explicit Q")
