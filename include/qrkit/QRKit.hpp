@@ -479,6 +479,67 @@ class BlockDiagonalSparseQR {
         dz.download(z);
         return z;
     }
+    // ---- the Levenberg-Marquardt step on the factors (qrk_bd_lm_*): what Eigen::LevenbergMarquardt does with matrixR(),
+    // colsPermutation() and Q^T f between two factorisations (examples/ellipse_fitting.cpp:257-280).  R and the permutation of the last
+    // factorisation are read on the device, Q never: these work after factorizeAndSolve() / factorizeApplyQtDevice() too.  qtb has
+    // rows() entries (Q^T b as returned in *QtB: the first cols() are used) or cols(); diag (cols() positive entries) may be null = ones.
+    // the kernel lmSolve() runs on this plan; contains "unsupported" where it would refuse
+    std::string lmKernelName() const {
+        assert(m_analysisIsok && "analyzePattern() should be called first");
+        return std::string(qrk_bd_lm_kernel_name(m_plan));
+    }
+    // the column norms of J from R, in the matrix's own column order: the diag an LM driver starts from (a zero stays zero)
+    Vector colNorms() const {
+        assert(m_isInitialized && "The factorization should be called first, use compute()");
+        Vector out((size_t)cols());
+        DeviceVec d(*this, out.size());
+        check(qrk_bd_r_col_norms(m_plan, (const double*)m_dr, (const int32_t*)m_dperm, d.ptr(), QRK_MEM_DEVICE));
+        d.download(out);
+        return out;
+    }
+    // g = P R^T (Q^T b) = J^T b in the matrix's column order; *gnorm = || D^-1 g ||
+    Vector lmGradient(const Vector& qtb, const Vector* diag = 0, double* gnorm = 0) const {
+        assert(m_isInitialized && "The factorization should be called first, use compute()");
+        Vector g((size_t)cols()), n2(1, 0.0);
+        DeviceVec y(*this, (size_t)cols()), dd(*this, (size_t)cols()), dg(*this, g.size()), dn(*this, (size_t)1);
+        uploadLm(qtb, diag, y, dd);
+        check(qrk_bd_lm_gradient(m_plan, (const double*)m_dr, (const int32_t*)m_dperm, y.ptr(), diag ? dd.ptr() : (double*)0, dg.ptr(),
+                                 dn.ptr(), QRK_MEM_DEVICE));
+        dg.download(g);
+        dn.download(n2);
+        if (gnorm) *gnorm = std::sqrt(n2[0]);
+        return g;
+    }
+    // x = argmin || R P^T x - Q^T b ||^2 + par || D x ||^2; sums (3 doubles, may be null): || D x ||^2, the sum of
+    // || S^-T D^2 z ||^2 over the tiles, the number of tiles with a zero on R's diagonal (include/qrkit_amd.h, qrk_bd_lm_solve)
+    Vector lmSolve(const Vector& qtb, const Vector* diag, double par, double* sums = 0) const {
+        assert(m_isInitialized && "The factorization should be called first, use compute()");
+        Vector x((size_t)cols()), s(3, 0.0);
+        DeviceVec y(*this, (size_t)cols()), dd(*this, (size_t)cols()), dx(*this, x.size()), ds(*this, (size_t)3);
+        uploadLm(qtb, diag, y, dd);
+        check(qrk_bd_lm_solve(m_plan, (const double*)m_dr, (const int32_t*)m_dperm, y.ptr(), diag ? dd.ptr() : (double*)0, par, dx.ptr(),
+                              sums ? ds.ptr() : (double*)0, QRK_MEM_DEVICE));
+        dx.download(x);
+        if (sums) { ds.download(s); sums[0] = s[0]; sums[1] = s[1]; sums[2] = s[2]; }
+        return x;
+    }
+    // MINPACK's lmpar (qrk_bd_lmpar): the step x with | || D x || - delta | <= 0.1 delta, or the Gauss-Newton step and par = 0 when
+    // that lies inside the region.  par: in the start value, out the result; *iters: passes of the loop; *trace: (par, || D x ||^2,
+    // sums[1]) of every evaluation.  Synchronises the stream once per evaluation.
+    Vector lmpar(const Vector& qtb, const Vector* diag, double delta, double& par, int* iters = 0, Vector* trace = 0) const {
+        assert(m_isInitialized && "The factorization should be called first, use compute()");
+        Vector x((size_t)cols());
+        DeviceVec y(*this, (size_t)cols()), dd(*this, (size_t)cols()), dx(*this, x.size());
+        uploadLm(qtb, diag, y, dd);
+        double tr[33];
+        int32_t it = 0;
+        check(qrk_bd_lmpar(m_plan, (const double*)m_dr, (const int32_t*)m_dperm, y.ptr(), diag ? dd.ptr() : (double*)0, delta, &par, dx.ptr(),
+                           &it, tr));
+        dx.download(x);
+        if (iters) *iters = (int)it;
+        if (trace) trace->assign(tr, tr + 3 * (it + 1));
+        return x;
+    }
     // matrixQ().transpose() * B on the device (test/test-qrkit.cpp:187)
     Vector applyQt(const Vector& B) const {
         needQ("applyQt()");
@@ -540,6 +601,14 @@ class BlockDiagonalSparseQR {
         if (buf) { qrk_device_free(m_handle, buf); buf = 0; cap = 0; }
         check(qrk_device_alloc(m_handle, bytes, &buf));
         cap = bytes;
+    }
+    // the first cols() entries of Q^T b and, when given, diag into device vectors of cols() entries (lmSolve / lmGradient / lmpar)
+    void uploadLm(const Vector& qtb, const Vector* diag, const DeviceVec& y, const DeviceVec& dd) const {
+        const size_t n = (size_t)cols();
+        if (qtb.size() != n && qtb.size() != (size_t)rows()) throw std::invalid_argument("qrkit: Q^T b must have rows() or cols() entries");
+        if (diag && diag->size() != n) throw std::invalid_argument("qrkit: diag must have cols() entries");
+        check(qrk_memcpy(m_handle, y.p, qtb.data(), (int64_t)(n * sizeof(double)), 0));
+        if (diag) check(qrk_memcpy(m_handle, dd.p, diag->data(), (int64_t)(n * sizeof(double)), 0));
     }
     void releaseDevice() {
         void** bufs[4] = {&m_dtiles, &m_dq, &m_dr, &m_dperm};

@@ -254,6 +254,63 @@ qrk_status qrk_bd_factorize_apply_qt(qrk_bd_plan plan, const double* tiles, cons
  * "fallback" on the explicit-Q route.  The pointer is static, like qrk_bd_kernel_name. */
 const char* qrk_bd_panel_kernel_name(qrk_bd_plan plan, int64_t ncols);
 
+/* ------------------------------------ block-diagonal: the Levenberg-Marquardt step on the factors */
+
+/* What Eigen::LevenbergMarquardt does between two factorisations (examples/ellipse_fitting.cpp:257-280,
+ * bench/bench_sparse_qr_extra.cpp:303-346): MINPACK's lmpar on matrixR(), colsPermutation() and Q^T f -- no tile, no Q, no
+ * reflector is read, so these work after qrk_bd_factorize_rhs / qrk_bd_factorize_apply_qt as after qrk_bd_factorize.  Common arguments:
+ *   r_vals [nnz_r], perm [mat_cols]  in : as qrk_bd_factorize wrote them (perm holds global column indices); the arrays are the
+ *                                         caller's, the plan's factorised state is not consulted
+ *   y      [mat_cols]                in : the first mat_cols entries of Q^T b in FullQ order (qtb[0:mat_cols] of
+ *                                         qrk_bd_factorize_rhs; what qrk_bd_apply_qt gives): tile t's entries at its base_col
+ *   diag   [mat_cols]                in : positive scale factors in the matrix's own column order; NULL = all ones
+ * FullQ plans whose tiles have at most 32 columns; otherwise QRK_STATUS_UNSUPPORTED (BlockDiagonalQ as qrk_bd_solve).  The first
+ * three are enqueue-only for QRK_MEM_DEVICE (no host synchronisation; par travels as a kernel argument) and stage like qrk_bd_solve
+ * for QRK_MEM_HOST.  Every sum is formed in a fixed order (one partial per workgroup in a scratch the plan owns -- allocated by the
+ * first call that asks for a sum, QRK_STATUS_ALLOC_FAILED if that fails -- then one workgroup over the partials; no floating-point
+ * atomics; the grid depends on the plan alone): two identical calls give identical bits. */
+
+/* The damped solve of MINPACK's qrsolv, tile by tile: x = argmin || R P^T x - y ||^2 + par || D x ||^2, par >= 0.  In the pivoted
+ * order of a tile, with Dt = D permuted: z = argmin || R_t z - y_t ||^2 + par || Dt z ||^2, x[perm[base_col + k]] = z_k.
+ *   sums[0] = || D x ||^2
+ *   sums[1] = sum over the tiles of || S_t^-T (Dt^2 z) ||^2, S_t^T S_t = R_t^T R_t + par Dt^2 (the derivative lmpar's Newton step needs)
+ *   sums[2] = number of tiles with an exact zero on R's diagonal
+ * sums (3 doubles) may be NULL.  A tile whose S has its first exact zero diagonal entry at k0 (par = 0: S = R) gets z_k = 0 for
+ * k >= k0 and the solution of the leading k0 x k0 block -- MINPACK's nsing rule per tile -- and adds nothing to sums[1]. */
+qrk_status qrk_bd_lm_solve(qrk_bd_plan plan, const double* r_vals, const int32_t* perm, const double* y, const double* diag,
+                           double par, double* x, double* sums, qrk_memspace space);
+
+/* g = P R^T y = J^T f in the matrix's column order, g[perm[base_col + k]] = sum_{i <= k} R(i, k) y_i, and *gnorm2 =
+ * sum (g_j / diag_j)^2 (lmpar's upper bound is sqrt(gnorm2) / delta).  g [mat_cols] or gnorm2 may be NULL, not both. */
+qrk_status qrk_bd_lm_gradient(qrk_bd_plan plan, const double* r_vals, const int32_t* perm, const double* y, const double* diag,
+                              double* g, double* gnorm2, qrk_memspace space);
+
+/* norms[perm[base_col + k]] = || R_t(0:k, k) || = the norm of column perm[base_col + k] of J: the diag an LM driver starts from
+ * (LevenbergMarquardt::minimizeInit takes them from colsPermutation() and matrixR()).  An exact zero is written as zero; the
+ * caller decides what to put in its place. */
+qrk_status qrk_bd_r_col_norms(qrk_bd_plan plan, const double* r_vals, const int32_t* perm, double* norms, qrk_memspace space);
+
+/* MINPACK's lmpar (what LevenbergMarquardt::minimizeOneStep calls for the step, examples/ellipse_fitting.cpp:257-280) run on the
+ * host over the calls above: finds par with | || D x || - delta | <= 0.1 delta, or par = 0 when the Gauss-Newton step is inside
+ * the region.  DEVICE pointers only (r_vals, perm, y, diag, x); par (in: start value, out: result), iters and trace are HOST.
+ * Every evaluation reads the sums back into a pinned buffer of the plan, so the call SYNCHRONISES the handle's stream once per
+ * evaluation (at most 11 times) and cannot be captured into a hipGraph.  x holds the step of the returned par on return.
+ *   1  evaluate at par = 0: s = sums; dxnorm = sqrt(s0), fp = dxnorm - delta; fp <= 0.1 delta: par = 0, iters = 0, return
+ *   2  parl = 0 if s2 > 0, else fp / (delta s1 / s0)
+ *   3  gnorm = sqrt(gnorm2) of qrk_bd_lm_gradient; paru = gnorm / delta; paru = 0: paru = DBL_MIN / min(delta, 0.1)
+ *   4  par = min(max(par, parl), paru); par = 0: par = gnorm / dxnorm
+ *   5  for iter = 1, 2, ...: par = 0: par = max(DBL_MIN, 0.001 paru); evaluate at par; dxnorm = sqrt(s0), temp = fp,
+ *      fp = dxnorm - delta; stop if |fp| <= 0.1 delta, or (parl = 0 and fp <= temp and temp < 0), or iter = 10; else
+ *      parc = fp / (delta s1 / s0); fp > 0: parl = max(parl, par); fp < 0: paru = min(paru, par); par = max(parl, par + parc)
+ * trace (3 x 11 doubles, may be NULL) receives (par, s0, s1) of every evaluation, the one at par = 0 first; *iters (may be NULL) =
+ * the number of passes of the loop.  delta > 0, *par >= 0. */
+qrk_status qrk_bd_lmpar(qrk_bd_plan plan, const double* r_vals, const int32_t* perm, const double* y, const double* diag,
+                        double delta, double* par, double* x, int32_t* iters, double* trace);
+
+/* Name of the kernel qrk_bd_lm_solve runs on this plan, or a string that contains "unsupported" where it would refuse.  The
+ * pointer is static, like qrk_bd_kernel_name. */
+const char* qrk_bd_lm_kernel_name(qrk_bd_plan plan);
+
 /* --------------------------------------------- dense right-block solver (angular) */
 
 /* A single dense Householder QR with implicit Q: the _BlockQRSolverRight of

@@ -107,6 +107,10 @@ struct qrk_bd_plan_s {
     int64_t exact_ws_stride = 0;
     int exact_num_wg = 0, exact_maxr = 0, exact_maxc = 0;
     double* d_q_scratch = nullptr;       // qrk_bd_factorize_rhs on a plan without a Q-less kernel: nnz_q doubles, allocated on first use
+    // qrk_bd_lm_* (bd_lm.hip): one partial per workgroup and sum (3 * BD_LM_MAX_BLOCKS doubles) followed by the four sums qrk_bd_lmpar
+    // reads back; allocated on first use.  h_lm_sums: their pinned host copy (qrk_bd_lmpar only)
+    double* d_lm_scratch = nullptr;
+    double* h_lm_sums = nullptr;
 };
 
 // One size class of the mid-size tiles: on chip (bdqr_reg.hip) when all of its tiles are wider than 64 columns, else bdqr_col.hip
@@ -600,6 +604,43 @@ qrk_status enqueue_factorize_apply_qt(qrk_bd_plan_s* p, const double* tiles, con
     return QRK_STATUS_OK;
 }
 
+// The plan's scratch of the Levenberg-Marquardt kernels, allocated by the first call that asks for a sum
+qrk_status ensure_lm_scratch(qrk_bd_plan_s* p, const char* who)
+{
+    if (p->d_lm_scratch) return QRK_STATUS_OK;
+    if (hipMalloc((void**)&p->d_lm_scratch, (size_t)(3 * qrk::BD_LM_MAX_BLOCKS + 4) * sizeof(double)) != hipSuccess) {
+        p->d_lm_scratch = nullptr;
+        (void)hipGetLastError();
+        return fail(p->h, QRK_STATUS_ALLOC_FAILED, std::string(who) + ": cannot allocate the plan's scratch of partial sums");
+    }
+    return QRK_STATUS_OK;
+}
+
+// Why qrk_bd_lm_* refuse this plan (nullptr: they do not)
+const char* lm_unsupported(const qrk_bd_plan_s* p)
+{
+    if (p->q_format != QRK_FULL_Q) return "R is upper triangular only in the FullQ format (BlockDiagonalSparseQR.h:134-154)";
+    if (qrk::bd_lm_group_width(p->max_cols) < 0) return "a tile of this plan has more than 32 columns";
+    return nullptr;
+}
+
+// The damped solve on the handle's stream, device pointers; sums (device, 3 doubles) may be null
+qrk_status enqueue_lm_solve(qrk_bd_plan_s* p, const double* r, const int32_t* perm, const double* y, const double* diag, double par,
+                            double* x, double* sums)
+{
+    if (sums) if (qrk_status st = ensure_lm_scratch(p, "qrk_bd_lm_solve")) return st;
+    QRK_HIP(p->h, qrk::launch_bd_lm_solve(make_geom(p), p->max_cols, r, perm, y, diag, par, x, p->d_lm_scratch, sums, p->h->stream));
+    return QRK_STATUS_OK;
+}
+
+qrk_status enqueue_lm_gradient(qrk_bd_plan_s* p, const double* r, const int32_t* perm, const double* y, const double* diag, double* g,
+                               double* gnorm2)
+{
+    if (gnorm2) if (qrk_status st = ensure_lm_scratch(p, "qrk_bd_lm_gradient")) return st;
+    QRK_HIP(p->h, qrk::launch_bd_lm_gradient(make_geom(p), p->max_cols, r, perm, y, diag, g, p->d_lm_scratch, gnorm2, p->h->stream));
+    return QRK_STATUS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -956,7 +997,8 @@ qrk_status qrk_bd_plan_destroy(qrk_bd_plan p)
     (void)hipFree(p->d_toff); (void)hipFree(p->d_qoff); (void)hipFree(p->d_roff); (void)hipFree(p->d_wave_ids); (void)hipFree(p->d_w64_ids);
     (void)hipFree(p->d_wg_ids); (void)hipFree(p->d_workspace);
     (void)hipFree(p->d_col_ids); (void)hipFree(p->d_col_workspace); (void)hipFree(p->d_redo); (void)hipFree(p->d_exact_ws);
-    (void)hipFree(p->d_p4_scratch); (void)hipFree(p->d_q_scratch);
+    (void)hipFree(p->d_p4_scratch); (void)hipFree(p->d_q_scratch); (void)hipFree(p->d_lm_scratch);
+    if (p->h_lm_sums) (void)hipHostFree(p->h_lm_sums);
     delete p;
     return QRK_STATUS_OK;
 }
@@ -1305,6 +1347,148 @@ const char* qrk_bd_panel_kernel_name(qrk_bd_plan p, int64_t ncols)
         return piv ? "qrk::thin_panel::bdqr_thin_panel_kernel<true, 16, 1>" : "qrk::thin_panel::bdqr_thin_panel_kernel<false, 16, 1>";
     }
     return "fallback: qrk_bd_factorize + qrk_bd_apply_qt through the plan's Q scratch";
+}
+
+qrk_status qrk_bd_lm_solve(qrk_bd_plan p, const double* r_vals, const int32_t* perm, const double* y, const double* diag, double par,
+                           double* x, double* sums, qrk_memspace space)
+{
+    if (!p || !r_vals || !perm || !y || !x || !(par >= 0.0))
+        return fail(p ? p->h : nullptr, QRK_STATUS_INVALID_ARGUMENT, "qrk_bd_lm_solve: bad argument (NULL buffer, par < 0 or NaN)");
+    qrk_handle h = p->h;
+    if (const char* why = lm_unsupported(p)) return fail(h, QRK_STATUS_UNSUPPORTED, std::string("qrk_bd_lm_solve: ") + why);
+    QRK_HIP(h, hipSetDevice(h->device));
+    if (space == QRK_MEM_DEVICE) return enqueue_lm_solve(p, r_vals, perm, y, diag, par, x, sums);
+    Staging s(h);
+    double *d_r, *d_y, *d_d, *d_x, *d_s = nullptr;
+    int32_t* d_p;
+    qrk_status st;
+    if ((st = s.in(r_vals, p->nnz_r, &d_r)) || (st = s.in(perm, (int64_t)p->mat_cols, &d_p)) || (st = s.in(y, (int64_t)p->mat_cols, &d_y)) ||
+        (st = s.in(diag, (int64_t)p->mat_cols, &d_d)) || (st = s.out((int64_t)p->mat_cols, &d_x)))
+        return st;
+    if (sums && (st = s.out(3, &d_s))) return st;
+    if ((st = enqueue_lm_solve(p, d_r, d_p, d_y, d_d, par, d_x, d_s))) return st;
+    if ((st = s.back(x, d_x, (int64_t)p->mat_cols)) || (st = s.back(sums, d_s, 3))) return st;
+    QRK_HIP(h, hipStreamSynchronize(h->stream));
+    return QRK_STATUS_OK;
+}
+
+qrk_status qrk_bd_lm_gradient(qrk_bd_plan p, const double* r_vals, const int32_t* perm, const double* y, const double* diag, double* g,
+                              double* gnorm2, qrk_memspace space)
+{
+    if (!p || !r_vals || !perm || !y || (!g && !gnorm2))
+        return fail(p ? p->h : nullptr, QRK_STATUS_INVALID_ARGUMENT, "qrk_bd_lm_gradient: bad argument (NULL buffer, or neither g nor gnorm2)");
+    qrk_handle h = p->h;
+    if (const char* why = lm_unsupported(p)) return fail(h, QRK_STATUS_UNSUPPORTED, std::string("qrk_bd_lm_gradient: ") + why);
+    QRK_HIP(h, hipSetDevice(h->device));
+    if (space == QRK_MEM_DEVICE) return enqueue_lm_gradient(p, r_vals, perm, y, diag, g, gnorm2);
+    Staging s(h);
+    double *d_r, *d_y, *d_d, *d_g = nullptr, *d_n = nullptr;
+    int32_t* d_p;
+    qrk_status st;
+    if ((st = s.in(r_vals, p->nnz_r, &d_r)) || (st = s.in(perm, (int64_t)p->mat_cols, &d_p)) || (st = s.in(y, (int64_t)p->mat_cols, &d_y)) ||
+        (st = s.in(diag, (int64_t)p->mat_cols, &d_d)))
+        return st;
+    if (g && (st = s.out((int64_t)p->mat_cols, &d_g))) return st;
+    if (gnorm2 && (st = s.out(1, &d_n))) return st;
+    if ((st = enqueue_lm_gradient(p, d_r, d_p, d_y, d_d, d_g, d_n))) return st;
+    if ((st = s.back(g, d_g, (int64_t)p->mat_cols)) || (st = s.back(gnorm2, d_n, 1))) return st;
+    QRK_HIP(h, hipStreamSynchronize(h->stream));
+    return QRK_STATUS_OK;
+}
+
+qrk_status qrk_bd_r_col_norms(qrk_bd_plan p, const double* r_vals, const int32_t* perm, double* norms, qrk_memspace space)
+{
+    if (!p || !r_vals || !perm || !norms)
+        return fail(p ? p->h : nullptr, QRK_STATUS_INVALID_ARGUMENT, "qrk_bd_r_col_norms: bad argument");
+    qrk_handle h = p->h;
+    if (const char* why = lm_unsupported(p)) return fail(h, QRK_STATUS_UNSUPPORTED, std::string("qrk_bd_r_col_norms: ") + why);
+    QRK_HIP(h, hipSetDevice(h->device));
+    const qrk::TileGeom g = make_geom(p);
+    if (space == QRK_MEM_DEVICE) {
+        QRK_HIP(h, qrk::launch_bd_r_col_norms(g, p->max_cols, r_vals, perm, norms, h->stream));
+        return QRK_STATUS_OK;
+    }
+    Staging s(h);
+    double *d_r, *d_n;
+    int32_t* d_p;
+    qrk_status st;
+    if ((st = s.in(r_vals, p->nnz_r, &d_r)) || (st = s.in(perm, (int64_t)p->mat_cols, &d_p)) || (st = s.out((int64_t)p->mat_cols, &d_n)))
+        return st;
+    QRK_HIP(h, qrk::launch_bd_r_col_norms(g, p->max_cols, d_r, d_p, d_n, h->stream));
+    if ((st = s.back(norms, d_n, (int64_t)p->mat_cols))) return st;
+    QRK_HIP(h, hipStreamSynchronize(h->stream));
+    return QRK_STATUS_OK;
+}
+
+// MINPACK's lmpar on the host over the device primitives: include/qrkit_amd.h spells out the loop
+qrk_status qrk_bd_lmpar(qrk_bd_plan p, const double* r_vals, const int32_t* perm, const double* y, const double* diag, double delta,
+                        double* par, double* x, int32_t* iters, double* trace)
+{
+    if (!p || !r_vals || !perm || !y || !x || !par || !(delta > 0.0) || !(*par >= 0.0))
+        return fail(p ? p->h : nullptr, QRK_STATUS_INVALID_ARGUMENT, "qrk_bd_lmpar: bad argument (NULL buffer, delta <= 0, par < 0 or NaN)");
+    qrk_handle h = p->h;
+    if (const char* why = lm_unsupported(p)) return fail(h, QRK_STATUS_UNSUPPORTED, std::string("qrk_bd_lmpar: ") + why);
+    QRK_HIP(h, hipSetDevice(h->device));
+    if (qrk_status st = ensure_lm_scratch(p, "qrk_bd_lmpar")) return st;
+    if (!p->h_lm_sums && hipHostMalloc((void**)&p->h_lm_sums, 4 * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+        p->h_lm_sums = nullptr;
+        (void)hipGetLastError();
+        return fail(h, QRK_STATUS_ALLOC_FAILED, "qrk_bd_lmpar: cannot allocate the pinned buffer of the sums");
+    }
+    double* const d_sums = p->d_lm_scratch + 3 * qrk::BD_LM_MAX_BLOCKS;    // s0, s1, s2, gnorm2
+    double* const hs = p->h_lm_sums;
+    int evals = 0;
+    // one evaluation = one damped solve and one synchronisation of the stream (the first one also brings |D^-1 g|^2)
+    auto evaluate = [&](double pv, bool with_gradient) -> qrk_status {
+        if (qrk_status st = enqueue_lm_solve(p, r_vals, perm, y, diag, pv, x, d_sums)) return st;
+        if (with_gradient) if (qrk_status st = enqueue_lm_gradient(p, r_vals, perm, y, diag, nullptr, d_sums + 3)) return st;
+        QRK_HIP(h, hipMemcpyAsync(hs, d_sums, (with_gradient ? 4 : 3) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        QRK_HIP(h, hipStreamSynchronize(h->stream));
+        if (trace) { trace[3 * evals] = pv; trace[3 * evals + 1] = hs[0]; trace[3 * evals + 2] = hs[1]; }
+        ++evals;
+        return QRK_STATUS_OK;
+    };
+    if (iters) *iters = 0;
+    if (qrk_status st = evaluate(0.0, true)) return st;
+    double dxnorm = std::sqrt(hs[0]);
+    double fp = dxnorm - delta;
+    if (fp <= 0.1 * delta) { *par = 0.0; return QRK_STATUS_OK; }
+    // bounds: the Newton step of phi at zero where R is nonsingular, |D^-1 g| / delta above
+    double parl = (hs[2] > 0.0 || !(hs[1] > 0.0)) ? 0.0 : fp / (delta * hs[1] / hs[0]);
+    const double gnorm = std::sqrt(hs[3]);
+    double paru = gnorm / delta;
+    if (paru == 0.0) paru = DBL_MIN / std::min(delta, 0.1);
+    double pv = std::min(std::max(*par, parl), paru);
+    if (pv == 0.0) pv = gnorm / dxnorm;
+    for (int iter = 1;; ++iter) {
+        if (pv == 0.0) pv = std::max(DBL_MIN, 0.001 * paru);
+        if (qrk_status st = evaluate(pv, false)) return st;
+        dxnorm = std::sqrt(hs[0]);
+        const double temp = fp;
+        fp = dxnorm - delta;
+        if (iters) *iters = iter;
+        if (std::fabs(fp) <= 0.1 * delta || (parl == 0.0 && fp <= temp && temp < 0.0) || iter == 10) break;
+        const double parc = fp / (delta * hs[1] / hs[0]);
+        if (fp > 0.0) parl = std::max(parl, pv);
+        if (fp < 0.0) paru = std::min(paru, pv);
+        pv = std::max(parl, pv + parc);
+    }
+    *par = pv;
+    return QRK_STATUS_OK;
+}
+
+const char* qrk_bd_lm_kernel_name(qrk_bd_plan p)
+{
+    if (!p) return "";
+    if (p->q_format != QRK_FULL_Q) return "unsupported: R is upper triangular only in the FullQ format";
+    switch (qrk::bd_lm_group_width(p->max_cols)) {
+    case 0: return "qrk::lm::bd_lm_thin_kernel";
+    case 8: return "qrk::lm::bd_lm_group_kernel<8>";
+    case 16: return "qrk::lm::bd_lm_group_kernel<16>";
+    case 32: return "qrk::lm::bd_lm_group_kernel<32>";
+    case 64: return "qrk::lm::bd_lm_group_kernel<64>";
+    default: return "unsupported: a tile of this plan has more than 32 columns";
+    }
 }
 
 qrk_status qrk_dense_plan_create(qrk_handle h, int32_t rows, int32_t cols, qrk_block_solver solver,

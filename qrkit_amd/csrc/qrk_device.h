@@ -244,6 +244,16 @@ void launch_bd_solve_r(const TileGeom& g, int max_cols, const double* r_vals, co
 void launch_bd_solve(const TileGeom& g, int max_cols, const double* q_vals, const double* r_vals,
                      const int32_t* perm, const double* b, int64_t nrhs, double* x,
                      hipStream_t stream);
+// bd_lm.hip: the Levenberg-Marquardt step on R, the permutation and Q^T f (MINPACK lmpar's device primitives).  Tiles of at most 32
+// columns.  partials: 3 * BD_LM_MAX_BLOCKS doubles of scratch (one partial per workgroup and sum; only read when sums / gnorm2 is given)
+constexpr int BD_LM_MAX_BLOCKS = 4096;
+int bd_lm_group_width(int max_cols);      // 0: one lane per tile; 8 / 16 / 32 / 64 lanes per tile; -1: not supported
+hipError_t launch_bd_lm_solve(const TileGeom& g, int max_cols, const double* r_vals, const int32_t* perm, const double* y,
+                              const double* diag, double par, double* x, double* partials, double* sums, hipStream_t stream);
+hipError_t launch_bd_lm_gradient(const TileGeom& g, int max_cols, const double* r_vals, const int32_t* perm, const double* y,
+                                 const double* diag, double* gout, double* partials, double* gnorm2, hipStream_t stream);
+hipError_t launch_bd_r_col_norms(const TileGeom& g, int max_cols, const double* r_vals, const int32_t* perm, double* norms,
+                                 hipStream_t stream);
 
 // ---- decision margins of the fast kernels ------------------------------------------------
 // A fast kernel (FMA chains, squared column norms, un-normalised reflector) takes a data-dependent decision of the reference

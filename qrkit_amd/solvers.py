@@ -487,6 +487,90 @@ class BlockDiagonalSparseQR:
                                              capi.MEM_DEVICE), self._ctx.handle)
         return self._out(z, was_np, shape, self._cols)
 
+    # -- the Levenberg-Marquardt step on the factors (qrk_bd_lm_*; MINPACK's lmpar, the consumer of matrixR() / colsPermutation() /
+    #    Q^T f in Eigen::LevenbergMarquardt, examples/ellipse_fitting.cpp:257-280).  They read R and the permutation of the last
+    #    factorisation, never Q: they work after factorizeAndSolve() / factorizeApplyQtDevice() as after factorize().
+    def _lm_vec(self, v, what):
+        """(float64 device vector of cols() entries, was_numpy); `v` has cols() entries, or rows() (Q^T b: the first cols() are used)"""
+        was_np = not isinstance(v, torch.Tensor)
+        t = torch.as_tensor(np.asarray(v, dtype=np.float64)) if was_np else v
+        t = t.reshape(-1)
+        assert t.numel() in (self._cols, self._rows), f"{what}: expected cols() or rows() entries"
+        return t[:self._cols].to(self._ctx.device, torch.float64).contiguous(), was_np
+
+    def _lm_diag(self, diag):
+        if diag is None:
+            return None
+        d, _ = self._lm_vec(diag, "diag")
+        assert d.numel() == self._cols, "diag: expected cols() entries"
+        return d
+
+    def lmKernelName(self) -> str:
+        """The kernel lmSolve() runs on this plan (qrk_bd_lm_kernel_name); contains 'unsupported' where it would refuse."""
+        assert self.m_analysisIsok, "analyzePattern() should be called first"
+        return capi.lib().qrk_bd_lm_kernel_name(self._plan).decode()
+
+    def colNormsDevice(self) -> torch.Tensor:
+        """The column norms of J from R (qrk_bd_r_col_norms), in the matrix's own column order, on the device."""
+        assert self.m_isInitialized, "The factorization should be called first, use compute()"
+        out = torch.empty(max(self._cols, 1), dtype=torch.float64, device=self._ctx.device)
+        self._ctx.use_current_stream()
+        capi.check(capi.lib().qrk_bd_r_col_norms(self._plan, self._r.data_ptr(), self._perm.data_ptr(), out.data_ptr(), capi.MEM_DEVICE),
+                   self._ctx.handle)
+        return out[:self._cols]
+
+    def colNorms(self) -> np.ndarray:
+        """colNormsDevice() as a numpy array: the diag an LM driver starts from (an exact zero stays zero)."""
+        return self.colNormsDevice().cpu().numpy()
+
+    def lmGradient(self, qtb, diag=None):
+        """(g, gnorm): g = P R^T (Q^T b) = J^T b in the matrix's column order and gnorm = || D^-1 g || (qrk_bd_lm_gradient)."""
+        assert self.m_isInitialized, "The factorization should be called first, use compute()"
+        y, was_np = self._lm_vec(qtb, "qtb")
+        d = self._lm_diag(diag)
+        g = torch.empty(max(self._cols, 1), dtype=torch.float64, device=self._ctx.device)
+        n2 = torch.empty(1, dtype=torch.float64, device=self._ctx.device)
+        self._ctx.use_current_stream()
+        capi.check(capi.lib().qrk_bd_lm_gradient(self._plan, self._r.data_ptr(), self._perm.data_ptr(), y.data_ptr(),
+                                                 d.data_ptr() if d is not None else None, g.data_ptr(), n2.data_ptr(), capi.MEM_DEVICE),
+                   self._ctx.handle)
+        g = g[:self._cols]
+        return (g.cpu().numpy() if was_np else g), float(np.sqrt(n2.item()))
+
+    def lmSolve(self, qtb, diag, par: float, returnSums: bool = False):
+        """x = argmin || R P^T x - Q^T b ||^2 + par || D x ||^2 (qrk_bd_lm_solve; diag=None: D = I).  With returnSums also the three
+        sums as a numpy array: || D x ||^2, sum || S^-T D^2 z ||^2 per tile, tiles with a zero on R's diagonal."""
+        assert self.m_isInitialized, "The factorization should be called first, use compute()"
+        y, was_np = self._lm_vec(qtb, "qtb")
+        d = self._lm_diag(diag)
+        x = torch.empty(max(self._cols, 1), dtype=torch.float64, device=self._ctx.device)
+        sums = torch.empty(3, dtype=torch.float64, device=self._ctx.device) if returnSums else None
+        self._ctx.use_current_stream()
+        capi.check(capi.lib().qrk_bd_lm_solve(self._plan, self._r.data_ptr(), self._perm.data_ptr(), y.data_ptr(),
+                                              d.data_ptr() if d is not None else None, float(par), x.data_ptr(),
+                                              sums.data_ptr() if returnSums else None, capi.MEM_DEVICE), self._ctx.handle)
+        x = x[:self._cols]
+        xo = x.cpu().numpy() if was_np else x
+        return (xo, sums.cpu().numpy()) if returnSums else xo
+
+    def lmpar(self, qtb, diag, delta: float, par: float = 0.0, returnTrace: bool = False):
+        """MINPACK's lmpar (qrk_bd_lmpar): (par, x, iters) with | || D x || - delta | <= 0.1 delta, or par = 0 when the Gauss-Newton step
+        lies inside the region; `par` is the start value.  returnTrace adds the (par, || D x ||^2, sums[1]) of every evaluation as
+        an (evaluations, 3) array.  Synchronises the stream once per evaluation."""
+        assert self.m_isInitialized, "The factorization should be called first, use compute()"
+        y, was_np = self._lm_vec(qtb, "qtb")
+        d = self._lm_diag(diag)
+        x = torch.empty(max(self._cols, 1), dtype=torch.float64, device=self._ctx.device)
+        pv, it = C.c_double(float(par)), C.c_int32(0)
+        trace = (C.c_double * 33)()
+        self._ctx.use_current_stream()
+        capi.check(capi.lib().qrk_bd_lmpar(self._plan, self._r.data_ptr(), self._perm.data_ptr(), y.data_ptr(),
+                                           d.data_ptr() if d is not None else None, float(delta), C.byref(pv), x.data_ptr(), C.byref(it),
+                                           trace), self._ctx.handle)
+        x = x[:self._cols]
+        out = (pv.value, x.cpu().numpy() if was_np else x, it.value)
+        return out + (np.array(trace[:3 * (it.value + 1)]).reshape(-1, 3),) if returnTrace else out
+
     # -- helpers ---------------------------------------------------------------------------
     def _rhs(self, B, n):
         was_np = not isinstance(B, torch.Tensor)
