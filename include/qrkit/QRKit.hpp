@@ -15,6 +15,7 @@
 #include <cassert>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -539,6 +540,31 @@ class BlockDiagonalSparseQR {
         if (iters) *iters = (int)it;
         if (trace) trace->assign(tr, tr + 3 * (it + 1));
         return x;
+    }
+    // lmpar() on qrk_bd_lmpar_device: the same contract and the same par, iters, trace and x, but the whole search is one enqueue --
+    // delta and par go up in one copy, the results (par, iters, trace, x) come back in one: one synchronisation for the search
+    // instead of one per evaluation.  Throws std::invalid_argument for delta <= 0, par < 0 or NaN (the device call would report
+    // iters = -1).
+    Vector lmparDevice(const Vector& qtb, const Vector* diag, double delta, double& par, int* iters = 0, Vector* trace = 0) const {
+        assert(m_isInitialized && "The factorization should be called first, use compute()");
+        if (!(delta > 0.0) || !(par >= 0.0)) throw std::invalid_argument("qrkit: lmparDevice: delta must be positive and par non-negative");
+        // one device block: delta, par, iters (an int32 in a slot of its own), trace (33), x (cols())
+        const size_t n = (size_t)cols(), head = 36;
+        DeviceVec y(*this, n), dd(*this, n), blk(*this, head + n);
+        uploadLm(qtb, diag, y, dd);
+        Vector host(head + n, 0.0);
+        host[0] = delta; host[1] = par;
+        check(qrk_memcpy(m_handle, blk.p, host.data(), (int64_t)(2 * sizeof(double)), 0));
+        double* const b = blk.ptr();
+        check(qrk_bd_lmpar_device(m_plan, (const double*)m_dr, (const int32_t*)m_dperm, y.ptr(), diag ? dd.ptr() : (double*)0, b, b + 1,
+                                  b + head, (int32_t*)(b + 2), b + 3));
+        blk.download(host);
+        int32_t it = 0;
+        std::memcpy(&it, &host[2], sizeof(it));
+        par = host[1];
+        if (iters) *iters = (int)it;
+        if (trace) trace->assign(host.begin() + 3, host.begin() + 3 + 3 * (it + 1));
+        return Vector(host.begin() + (std::ptrdiff_t)head, host.end());
     }
     // matrixQ().transpose() * B on the device (test/test-qrkit.cpp:187)
     Vector applyQt(const Vector& B) const {

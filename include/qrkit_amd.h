@@ -294,7 +294,7 @@ qrk_status qrk_bd_r_col_norms(qrk_bd_plan plan, const double* r_vals, const int3
  * host over the calls above: finds par with | || D x || - delta | <= 0.1 delta, or par = 0 when the Gauss-Newton step is inside
  * the region.  DEVICE pointers only (r_vals, perm, y, diag, x); par (in: start value, out: result), iters and trace are HOST.
  * Every evaluation reads the sums back into a pinned buffer of the plan, so the call SYNCHRONISES the handle's stream once per
- * evaluation (at most 11 times) and cannot be captured into a hipGraph.  x holds the step of the returned par on return.
+ * evaluation (at most 11 times) and cannot be captured into a hipGraph (qrk_bd_lmpar_device below can).  x holds the step of the returned par on return.
  *   1  evaluate at par = 0: s = sums; dxnorm = sqrt(s0), fp = dxnorm - delta; fp <= 0.1 delta: par = 0, iters = 0, return
  *   2  parl = 0 if s2 > 0, else fp / (delta s1 / s0)
  *   3  gnorm = sqrt(gnorm2) of qrk_bd_lm_gradient; paru = gnorm / delta; paru = 0: paru = DBL_MIN / min(delta, 0.1)
@@ -306,6 +306,31 @@ qrk_status qrk_bd_r_col_norms(qrk_bd_plan plan, const double* r_vals, const int3
  * the number of passes of the loop.  delta > 0, *par >= 0. */
 qrk_status qrk_bd_lmpar(qrk_bd_plan plan, const double* r_vals, const int32_t* perm, const double* y, const double* diag,
                         double delta, double* par, double* x, int32_t* iters, double* trace);
+
+/* qrk_bd_lmpar as ONE ENQUEUE: the same steps 1-5 with every stopping rule, the parl / paru bounds, the DBL_MIN cases and the cap of
+ * 10 passes, but the scalar part of each step runs in one lane on the device behind the sums of the evaluation.  The call
+ * enqueues a fixed chain on the handle's stream -- a memset of a small control block in the plan's scratch, the evaluation at
+ * par = 0 with the gradient sum, ten damped evaluations that return at once after the search has stopped -- and returns: no
+ * stream synchronisation, no copy to the host, no event query, so it can be captured into a hipGraph and replayed.
+ * ALL pointers are DEVICE pointers:
+ *   delta          in     : one double, the radius.  In device memory (not a kernel argument) so that a replayed graph sees a new one
+ *   par            in/out : one double: the start value on entry, the result once the stream has run the call
+ *   x   [mat_cols] out    : the step of the returned par once the stream has run the call
+ *   iters          out    : one int32, the number of passes of the loop (0 .. 10); may be NULL
+ *   trace [3 x 11] out    : (par, s0, s1) of every evaluation that ran, the one at par = 0 first; the rows of evaluations that did
+ *                           not run are zero; may be NULL
+ * The values of delta and par can only be checked on the device: if !(*delta > 0) or !(*par >= 0) (NaN included) the call writes
+ * *iters = -1, leaves *par as it was, runs no damped evaluation, and x HAS NO MEANING (it holds the undamped solve).  A NULL plan,
+ * r_vals, perm, y, delta, par or x is QRK_STATUS_INVALID_ARGUMENT before a device is touched; plan support is that of
+ * qrk_bd_lm_solve (QRK_STATUS_UNSUPPORTED otherwise).
+ * The only allocation is the plan's scratch of the LM calls, made by the first of them on the plan.  If it does not exist yet and
+ * the handle's stream is being captured the call fails with QRK_STATUS_INVALID_ARGUMENT: make one LM call on the plan outside
+ * the capture first.  The scratch (the control block included) belongs to the plan: calls on one plan must be ordered on one
+ * stream, as for every qrk_bd_lm_* call that asks for a sum.
+ * The sums are those of qrk_bd_lm_solve / qrk_bd_lm_gradient (same kernels' arithmetic, same grid, same order) and the scalar
+ * steps are the host loop's correctly rounded operations in the same order: par, iters, trace and x are qrk_bd_lmpar's. */
+qrk_status qrk_bd_lmpar_device(qrk_bd_plan plan, const double* r_vals, const int32_t* perm, const double* y, const double* diag,
+                               const double* delta, double* par, double* x, int32_t* iters, double* trace);
 
 /* Name of the kernel qrk_bd_lm_solve runs on this plan, or a string that contains "unsupported" where it would refuse.  The
  * pointer is static, like qrk_bd_kernel_name. */

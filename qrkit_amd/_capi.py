@@ -33,7 +33,7 @@ EXPORTS = (
     "qrk_shard_ranges", "qrk_gather_r", "qrk_gather_x",
     "qrk_bd_factorize_rhs", "qrk_bd_rhs_kernel_name",
     "qrk_bd_factorize_apply_qt", "qrk_bd_panel_kernel_name",
-    "qrk_bd_lm_solve", "qrk_bd_lm_gradient", "qrk_bd_r_col_norms", "qrk_bd_lmpar", "qrk_bd_lm_kernel_name",
+    "qrk_bd_lm_solve", "qrk_bd_lm_gradient", "qrk_bd_r_col_norms", "qrk_bd_lmpar", "qrk_bd_lmpar_device", "qrk_bd_lm_kernel_name",
 )
 
 
@@ -120,6 +120,8 @@ def lib() -> C.CDLL:
     L.qrk_bd_r_col_norms.argtypes = [vp, dp, ip, dp, C.c_int]
     L.qrk_bd_lmpar.restype = C.c_int
     L.qrk_bd_lmpar.argtypes = [vp, dp, ip, dp, dp, C.c_double, C.POINTER(C.c_double), dp, C.POINTER(C.c_int32), C.POINTER(C.c_double)]
+    L.qrk_bd_lmpar_device.restype = C.c_int
+    L.qrk_bd_lmpar_device.argtypes = [vp, dp, ip, dp, dp, dp, dp, dp, ip, dp]
     L.qrk_bd_lm_kernel_name.restype = C.c_char_p
     L.qrk_bd_lm_kernel_name.argtypes = [vp]
     L.qrk_dense_plan_create.restype = C.c_int

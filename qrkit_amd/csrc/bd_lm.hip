@@ -1,4 +1,5 @@
-// bd_lm.hip -- the Levenberg-Marquardt trust-region step on the factors of the block-diagonal solver.
+// bd_lm.hip -- the Levenberg-Marquardt trust-region step on the factors of the block-diagonal solver (DESIGN.md K9;
+// MINPACK's lmpar over them as one enqueue, its scalar steps on the device: K10).
 //
 // Between two factorisations Eigen::LevenbergMarquardt (examples/ellipse_fitting.cpp:257-280, bench/bench_sparse_qr_extra.cpp:303-346)
 // runs MINPACK's lmpar on matrixR(), colsPermutation() and Q^T f: up to ten times a damped solve
@@ -86,9 +87,11 @@ __device__ __forceinline__ void block_sum(double (&v)[N], double* red)
 }
 
 // ---- tiles with 1 or 2 columns: one lane per tile (the 10^6-tile LM shape; R is 1 or 3 doubles) ---------------------------------
-__global__ void __launch_bounds__(THREADS)
-bd_lm_thin_kernel(LmGeom g, const double* __restrict__ r_vals, const int32_t* __restrict__ perm, const double* __restrict__ y,
-                  const double* __restrict__ diag, double par, double* __restrict__ x, double* __restrict__ partials)
+// The body of bd_lm_thin_kernel (par a kernel argument) and of bd_lm_thin_ctl_kernel / bd_lm_thin_last_kernel (par from the control
+// block of the device-side lmpar, below)
+__device__ __forceinline__ void
+lm_thin_tiles(LmGeom g, const double* r_vals, const int32_t* perm, const double* y,
+              const double* diag, double par, double* x, double* partials)
 {
     __shared__ double red[12];
     const double sp = sqrt(par);
@@ -141,6 +144,23 @@ bd_lm_thin_kernel(LmGeom g, const double* __restrict__ r_vals, const int32_t* __
     }
 }
 
+__global__ void __launch_bounds__(THREADS)
+bd_lm_thin_kernel(LmGeom g, const double* __restrict__ r_vals, const int32_t* __restrict__ perm, const double* __restrict__ y,
+                  const double* __restrict__ diag, double par, double* __restrict__ x, double* __restrict__ partials)
+{
+    lm_thin_tiles(g, r_vals, perm, y, diag, par, x, partials);
+}
+
+// One damped evaluation of the device-side lmpar: nothing (x included) is touched once the search has stopped
+__global__ void __launch_bounds__(THREADS)
+bd_lm_thin_ctl_kernel(LmGeom g, const double* __restrict__ r_vals, const int32_t* __restrict__ perm, const double* __restrict__ y,
+                      const double* __restrict__ diag, const LmControl* __restrict__ ctl, double* __restrict__ x,
+                      double* __restrict__ partials)
+{
+    if (ctl->done) return;                            // (uniform loads: the control block is read through the scalar cache)
+    lm_thin_tiles(g, r_vals, perm, y, diag, ctl->par, x, partials);
+}
+
 // ---- tiles with up to 32 columns: a group of G lanes per tile ----------------------------------------------------------------------
 // Lane k of a group holds column k of R and of the lower part in registers (static indices: every loop is unrolled), the lane after
 // the last column holds the right-hand side as one more column -- so G > c: 8 / 16 / 32 lanes for up to 7 / 15 / 31 columns, the
@@ -163,10 +183,11 @@ __device__ __forceinline__ double group_bcast(double v, int src_lane, int k)
     return __shfl(v, src_lane, 64);
 }
 
+// The body of bd_lm_group_kernel<G>, bd_lm_group_ctl_kernel<G> and bd_lm_group_last_kernel<G>
 template <int G>
-__global__ void __launch_bounds__(THREADS)
-bd_lm_group_kernel(LmGeom g, const double* __restrict__ r_vals, const int32_t* __restrict__ perm, const double* __restrict__ y,
-                   const double* __restrict__ diag, double par, double* __restrict__ x, double* __restrict__ partials)
+__device__ __forceinline__ void
+lm_group_tiles(LmGeom g, const double* r_vals, const int32_t* perm, const double* y,
+               const double* diag, double par, double* x, double* partials)
 {
     constexpr int CM = G == 64 ? 32 : G - 1;          // widest tile of this instantiation
     constexpr int TPB = THREADS / G;                  // tiles per workgroup
@@ -307,17 +328,197 @@ bd_lm_group_kernel(LmGeom g, const double* __restrict__ r_vals, const int32_t* _
     }
 }
 
+template <int G>
+__global__ void __launch_bounds__(THREADS)
+bd_lm_group_kernel(LmGeom g, const double* __restrict__ r_vals, const int32_t* __restrict__ perm, const double* __restrict__ y,
+                   const double* __restrict__ diag, double par, double* __restrict__ x, double* __restrict__ partials)
+{
+    lm_group_tiles<G>(g, r_vals, perm, y, diag, par, x, partials);
+}
+
+template <int G>
+__global__ void __launch_bounds__(THREADS)
+bd_lm_group_ctl_kernel(LmGeom g, const double* __restrict__ r_vals, const int32_t* __restrict__ perm, const double* __restrict__ y,
+                       const double* __restrict__ diag, const LmControl* __restrict__ ctl, double* __restrict__ x,
+                       double* __restrict__ partials)
+{
+    if (ctl->done) return;
+    lm_group_tiles<G>(g, r_vals, perm, y, diag, ctl->par, x, partials);
+}
+
 // ---- the partials of `nblocks` workgroups (n sums each) added in a fixed order: one workgroup -------------------------------------
+// sum s of the n: every thread its partials b = threadIdx.x, threadIdx.x + 256, ... in that order, then block_sum (the same value in
+// every thread)
+__device__ __forceinline__ double lm_sum_partials(const double* __restrict__ partials, int nblocks, int n, int s, double* red)
+{
+    double v[1] = {0.0};
+    for (int b = threadIdx.x; b < nblocks; b += THREADS) v[0] += partials[(int64_t)b * n + s];
+    block_sum<1>(v, red);
+    return v[0];
+}
+
 __global__ void __launch_bounds__(THREADS)
 bd_lm_finish_kernel(const double* __restrict__ partials, int nblocks, int n, double* __restrict__ out)
 {
     __shared__ double red[4];
     for (int s = 0; s < n; ++s) {
-        double v[1] = {0.0};
-        for (int b = threadIdx.x; b < nblocks; b += THREADS) v[0] += partials[(int64_t)b * n + s];
-        block_sum<1>(v, red);
-        if (threadIdx.x == 0) out[s] = v[0];
+        const double v = lm_sum_partials(partials, nblocks, n, s, red);
+        if (threadIdx.x == 0) out[s] = v;
     }
+}
+
+// ---- the device-side lmpar (qrk_bd_lmpar_device): MINPACK's update of par as one lane's work behind the sums of an evaluation -------
+// The scalar arithmetic of qrk_bd_lmpar's host loop (capi.hip; include/qrkit_amd.h spells out steps 1-5) operation for operation:
+// correctly rounded sqrt and division, no contraction (there is no a * b + c in it, and the pragma keeps it so), std::min / std::max
+// as comparisons.
+__device__ __forceinline__ double lm_max(double a, double b) { return a < b ? b : a; }     // std::max(a, b)
+__device__ __forceinline__ double lm_min(double a, double b) { return b < a ? b : a; }     // std::min(a, b)
+constexpr double LM_DBL_MIN = 2.2250738585072014e-308;
+
+// Steps 1-4 behind the evaluation at par = 0: s = (s0, s1, s2) of that solve, gnorm2 = | D^-1 g |^2.  Leaves the control block ready
+// for the first damped evaluation, or done.
+__device__ void lm_control_first(LmControl* ctl, double s0, double s1, double s2, double gnorm2, const double* delta_p, double* par_p,
+                                 int32_t* iters, double* trace)
+{
+#pragma clang fp contract(off)
+    const double delta = *delta_p, par0 = *par_p;
+    if (trace) { trace[0] = 0.0; trace[1] = s0; trace[2] = s1; }
+    ctl->evals = 1;
+    ctl->done = 1;
+    if (!(delta > 0.0) || !(par0 >= 0.0)) {           // what qrk_bd_lmpar refuses on the host: *par stays, no damped evaluation
+        if (iters) *iters = -1;
+        return;
+    }
+    if (iters) *iters = 0;
+    const double dxnorm = sqrt(s0);
+    const double fp = dxnorm - delta;
+    if (fp <= 0.1 * delta) { *par_p = 0.0; return; }
+    const double parl = (s2 > 0.0 || !(s1 > 0.0)) ? 0.0 : fp / (delta * s1 / s0);
+    const double gnorm = sqrt(gnorm2);
+    double paru = gnorm / delta;
+    if (paru == 0.0) paru = LM_DBL_MIN / lm_min(delta, 0.1);
+    double pv = lm_min(lm_max(par0, parl), paru);
+    if (pv == 0.0) pv = gnorm / dxnorm;
+    if (pv == 0.0) pv = lm_max(LM_DBL_MIN, 0.001 * paru);         // (the head of pass 1)
+    ctl->par = pv; ctl->parl = parl; ctl->paru = paru; ctl->fp = fp; ctl->delta = delta; ctl->gnorm = gnorm;
+    ctl->done = 0;
+}
+
+// Step 5 behind damped evaluation number ctl->evals (= the pass of the loop): stop, or the next par
+__device__ void lm_control_pass(LmControl* ctl, double s0, double s1, double* par_p, int32_t* iters, double* trace)
+{
+#pragma clang fp contract(off)
+    const int iter = ctl->evals;
+    double pv = ctl->par, parl = ctl->parl, paru = ctl->paru;
+    const double delta = ctl->delta, temp = ctl->fp;
+    if (trace) { trace[3 * iter] = pv; trace[3 * iter + 1] = s0; trace[3 * iter + 2] = s1; }
+    const double dxnorm = sqrt(s0);
+    const double fp = dxnorm - delta;
+    if (iters) *iters = iter;
+    ctl->evals = iter + 1;
+    ctl->fp = fp;
+    if (fabs(fp) <= 0.1 * delta || (parl == 0.0 && fp <= temp && temp < 0.0) || iter == 10) {
+        *par_p = pv;
+        ctl->done = 1;
+        return;
+    }
+    const double parc = fp / (delta * s1 / s0);
+    if (fp > 0.0) parl = lm_max(parl, pv);
+    if (fp < 0.0) paru = lm_min(paru, pv);
+    pv = lm_max(parl, pv + parc);
+    if (pv == 0.0) pv = lm_max(LM_DBL_MIN, 0.001 * paru);         // (the head of the next pass)
+    ctl->par = pv; ctl->parl = parl; ctl->paru = paru;
+}
+
+// One workgroup behind the gradient's column kernel of evaluation 0 (FIRST: sums = s0, s1, s2 of the solve at par = 0, already
+// finished by bd_lm_finish_kernel; partials = the `nblocks` partials of | D^-1 g |^2; the unused rows of trace are cleared here) or
+// behind a damped solve (partials = its 3 `nblocks` partials).  The sums are bd_lm_finish_kernel's, bit for bit; lane 0 does the
+// control step.
+template <bool FIRST>
+__global__ void __launch_bounds__(THREADS)
+bd_lm_control_kernel(const double* __restrict__ partials, int nblocks, double* __restrict__ sums, LmControl* __restrict__ ctl,
+                     const double* __restrict__ delta, double* __restrict__ par, int32_t* __restrict__ iters,
+                     double* __restrict__ trace)
+{
+    __shared__ double red[4];
+    if (FIRST) {
+        const double gnorm2 = lm_sum_partials(partials, nblocks, 1, 0, red);
+        if (trace && threadIdx.x >= 3 && threadIdx.x < 33) trace[threadIdx.x] = 0.0;
+        if (threadIdx.x == 0) {
+            sums[3] = gnorm2;
+            lm_control_first(ctl, sums[0], sums[1], sums[2], gnorm2, delta, par, iters, trace);
+        }
+    } else {
+        if (ctl->done) return;
+        double s[3];
+        for (int i = 0; i < 3; ++i) s[i] = lm_sum_partials(partials, nblocks, 3, i, red);
+        if (threadIdx.x == 0) {
+            sums[0] = s[0]; sums[1] = s[1]; sums[2] = s[2];
+            lm_control_pass(ctl, s[0], s[1], par, iters, trace);
+        }
+    }
+}
+
+// ---- the same control step without a kernel of its own: the workgroup that arrives last does it ---------------------------------
+// Behind the partial of a damped solve (the hand-off of an in-launch reduction; nobody waits, a workgroup that is not last exits):
+// every wave drains its stores, the workgroup meets, lane 0 releases at agent scope and draws a ticket from the counter of this pass
+// (cleared with the control block at the start of the call); the workgroup that draws the last ticket acquires at agent scope and
+// then reads all partials -- added in bd_lm_finish_kernel's order, so the sums keep their bits -- and lane 0 does the control step.
+// Returns at once for every workgroup but that one.  fin: 4 doubles of LDS.
+struct LmResult {
+    double* sums;
+    double* par;
+    int32_t* iters;
+    double* trace;
+};
+
+__device__ __forceinline__ void lm_last_arriver(LmControl* ctl, int pass, const double* partials, const LmResult& out, double* fin)
+{
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const uint32_t ticket = __hip_atomic_fetch_add(&ctl->arrived[pass], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        fin[0] = ticket == gridDim.x - 1 ? 1.0 : 0.0;
+    }
+    __syncthreads();
+    const bool last = fin[0] != 0.0;
+    if (!last) return;
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __syncthreads();
+    double s[3];
+    for (int i = 0; i < 3; ++i) s[i] = lm_sum_partials(partials, (int)gridDim.x, 3, i, fin);
+    if (threadIdx.x == 0) {
+        out.sums[0] = s[0]; out.sums[1] = s[1]; out.sums[2] = s[2];
+        lm_control_pass(ctl, s[0], s[1], out.par, out.iters, out.trace);
+    }
+}
+
+__global__ void __launch_bounds__(THREADS)
+bd_lm_thin_last_kernel(LmGeom g, const double* __restrict__ r_vals, const int32_t* __restrict__ perm, const double* __restrict__ y,
+                       const double* __restrict__ diag, LmControl* ctl, double* __restrict__ x, double* partials, LmResult out)
+{
+    __shared__ double fin[4];
+    if (ctl->done) return;
+    const int pass = ctl->evals;                      // (read before any workgroup can have written the next one: that takes all tickets)
+    lm_thin_tiles(g, r_vals, perm, y, diag, ctl->par, x, partials);
+    lm_last_arriver(ctl, pass, partials, out, fin);
+}
+
+template <int G>
+__global__ void __launch_bounds__(THREADS)
+bd_lm_group_last_kernel(LmGeom g, const double* __restrict__ r_vals, const int32_t* __restrict__ perm, const double* __restrict__ y,
+                        const double* __restrict__ diag, LmControl* ctl, double* __restrict__ x, double* partials, LmResult out)
+{
+    __shared__ double fin[4];
+    if (ctl->done) return;
+    const int pass = ctl->evals;
+    lm_group_tiles<G>(g, r_vals, perm, y, diag, ctl->par, x, partials);
+    lm_last_arriver(ctl, pass, partials, out, fin);
 }
 
 // ---- g = P R^T y and the column norms of R: G lanes per tile (a power of two >= the widest tile), lane k = column k ----------------
@@ -397,6 +598,60 @@ hipError_t launch_bd_lm_solve(const TileGeom& g, int max_cols, const double* r_v
     }
 #undef QRK_LM_G
     if (sums) hipLaunchKernelGGL(lm::bd_lm_finish_kernel, dim3(1), dim3(lm::THREADS), 0, stream, partials, blocks, 3, sums);
+    return hipGetLastError();
+}
+
+static void lm_columns_grid(int64_t num_tiles, int max_cols, int& G, int& blocks);
+
+// MINPACK's lmpar as a fixed chain on the stream (qrk_bd_lmpar_device): no launch depends on a host decision.
+//   memset of the control block; evaluation 0 = the solve at par = 0 with its finish (the kernels and sums of launch_bd_lm_solve),
+//   the gradient's column kernel, bd_lm_control_kernel<true>; then ten damped evaluations, which return at once when the control
+//   block says done: bd_lm_*_last_kernel (last_arriver: the sums and the control step in the workgroup that arrives last), or
+//   bd_lm_*_ctl_kernel + bd_lm_control_kernel<false> (a kernel boundary in place of the hand-off).
+// scratch: the plan's (BD_LM_SCRATCH_DOUBLES); delta, par, iters, trace: device.
+hipError_t launch_bd_lmpar_device(const TileGeom& g, int max_cols, const double* r_vals, const int32_t* perm, const double* y,
+                                  const double* diag, const double* delta, double* par, double* x, int32_t* iters, double* trace,
+                                  double* scratch, bool last_arriver, hipStream_t stream)
+{
+    const int G = bd_lm_group_width(max_cols);
+    if (G < 0) return hipErrorInvalidValue;
+    double* const partials = scratch;
+    double* const sums = scratch + 3 * BD_LM_MAX_BLOCKS;
+    LmControl* const ctl = (LmControl*)(scratch + 3 * BD_LM_MAX_BLOCKS + 4);
+    hipError_t e = hipMemsetAsync(ctl, 0, sizeof(LmControl), stream);
+    if (e != hipSuccess) return e;
+    if ((e = launch_bd_lm_solve(g, max_cols, r_vals, perm, y, diag, 0.0, x, partials, sums, stream)) != hipSuccess) return e;
+    const lm::LmGeom lg = lm::lm_geom_of(g);
+    const bool any = g.num_tiles > 0;
+    int gblocks = 0;
+    if (any) {
+        int GC;
+        lm_columns_grid(g.num_tiles, max_cols, GC, gblocks);
+        hipLaunchKernelGGL(lm::bd_lm_columns_kernel<0>, dim3(gblocks), dim3(lm::THREADS), 0, stream, lg, GC, r_vals, perm, y, diag, (double*)nullptr,
+                           partials);
+    }
+    hipLaunchKernelGGL(lm::bd_lm_control_kernel<true>, dim3(1), dim3(lm::THREADS), 0, stream, partials, gblocks, sums, ctl, delta, par, iters, trace);
+    const int blocks = any ? lm_solve_blocks(g.num_tiles, G) : 0;
+    const lm::LmResult res{sums, par, iters, trace};
+    for (int pass = 1; pass <= 10 && any && last_arriver; ++pass) {
+#define QRK_LM_G(GG) case GG: hipLaunchKernelGGL((lm::bd_lm_group_last_kernel<GG>), dim3(blocks), dim3(lm::THREADS), 0, stream, lg, r_vals, perm, y, diag, ctl, x, partials, res); break;
+        switch (G) {
+        case 0: hipLaunchKernelGGL(lm::bd_lm_thin_last_kernel, dim3(blocks), dim3(lm::THREADS), 0, stream, lg, r_vals, perm, y, diag, ctl, x, partials, res); break;
+        QRK_LM_G(8) QRK_LM_G(16) QRK_LM_G(32) QRK_LM_G(64)
+        default: break;
+        }
+#undef QRK_LM_G
+    }
+    for (int pass = 1; pass <= 10 && any && !last_arriver; ++pass) {
+#define QRK_LM_G(GG) case GG: hipLaunchKernelGGL((lm::bd_lm_group_ctl_kernel<GG>), dim3(blocks), dim3(lm::THREADS), 0, stream, lg, r_vals, perm, y, diag, ctl, x, partials); break;
+        switch (G) {
+        case 0: hipLaunchKernelGGL(lm::bd_lm_thin_ctl_kernel, dim3(blocks), dim3(lm::THREADS), 0, stream, lg, r_vals, perm, y, diag, ctl, x, partials); break;
+        QRK_LM_G(8) QRK_LM_G(16) QRK_LM_G(32) QRK_LM_G(64)
+        default: break;
+        }
+#undef QRK_LM_G
+        hipLaunchKernelGGL(lm::bd_lm_control_kernel<false>, dim3(1), dim3(lm::THREADS), 0, stream, partials, blocks, sums, ctl, delta, par, iters, trace);
+    }
     return hipGetLastError();
 }
 

@@ -108,7 +108,8 @@ struct qrk_bd_plan_s {
     int exact_num_wg = 0, exact_maxr = 0, exact_maxc = 0;
     double* d_q_scratch = nullptr;       // qrk_bd_factorize_rhs on a plan without a Q-less kernel: nnz_q doubles, allocated on first use
     // qrk_bd_lm_* (bd_lm.hip): one partial per workgroup and sum (3 * BD_LM_MAX_BLOCKS doubles) followed by the four sums qrk_bd_lmpar
-    // reads back; allocated on first use.  h_lm_sums: their pinned host copy (qrk_bd_lmpar only)
+    // reads back and the control block of qrk_bd_lmpar_device (qrk::BD_LM_SCRATCH_DOUBLES in all); allocated on first use.
+    // h_lm_sums: the pinned host copy of the sums (qrk_bd_lmpar only)
     double* d_lm_scratch = nullptr;
     double* h_lm_sums = nullptr;
 };
@@ -608,7 +609,7 @@ qrk_status enqueue_factorize_apply_qt(qrk_bd_plan_s* p, const double* tiles, con
 qrk_status ensure_lm_scratch(qrk_bd_plan_s* p, const char* who)
 {
     if (p->d_lm_scratch) return QRK_STATUS_OK;
-    if (hipMalloc((void**)&p->d_lm_scratch, (size_t)(3 * qrk::BD_LM_MAX_BLOCKS + 4) * sizeof(double)) != hipSuccess) {
+    if (hipMalloc((void**)&p->d_lm_scratch, (size_t)qrk::BD_LM_SCRATCH_DOUBLES * sizeof(double)) != hipSuccess) {
         p->d_lm_scratch = nullptr;
         (void)hipGetLastError();
         return fail(p->h, QRK_STATUS_ALLOC_FAILED, std::string(who) + ": cannot allocate the plan's scratch of partial sums");
@@ -1474,6 +1475,33 @@ qrk_status qrk_bd_lmpar(qrk_bd_plan p, const double* r_vals, const int32_t* perm
         pv = std::max(parl, pv + parc);
     }
     *par = pv;
+    return QRK_STATUS_OK;
+}
+
+// MINPACK's lmpar as one enqueue: the same loop, its scalar part run by one lane on the device (bd_lm.hip, launch_bd_lmpar_device)
+qrk_status qrk_bd_lmpar_device(qrk_bd_plan p, const double* r_vals, const int32_t* perm, const double* y, const double* diag,
+                               const double* delta, double* par, double* x, int32_t* iters, double* trace)
+{
+    if (!p || !r_vals || !perm || !y || !delta || !par || !x)
+        return fail(p ? p->h : nullptr, QRK_STATUS_INVALID_ARGUMENT, "qrk_bd_lmpar_device: bad argument (NULL plan or buffer)");
+    qrk_handle h = p->h;
+    if (const char* why = lm_unsupported(p)) return fail(h, QRK_STATUS_UNSUPPORTED, std::string("qrk_bd_lmpar_device: ") + why);
+    QRK_HIP(h, hipSetDevice(h->device));
+    if (!p->d_lm_scratch) {
+        // the one allocation of the LM calls; never under a stream capture (hipMalloc would invalidate it)
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        QRK_HIP(h, hipStreamIsCapturing(h->stream, &cs));
+        if (cs != hipStreamCaptureStatusNone)
+            return fail(h, QRK_STATUS_INVALID_ARGUMENT, "qrk_bd_lmpar_device: the plan's scratch is not allocated yet and the stream is being "
+                                                        "captured: call it once outside the capture first");
+        if (qrk_status st = ensure_lm_scratch(p, "qrk_bd_lmpar_device")) return st;
+    }
+    // The control step is a kernel of its own behind every solve.  QRK_LMPAR_CONTROL=last (read at every call) gives it to the solve's
+    // last-arriving workgroup instead: measured slower from a few hundred workgroups on, kept for that measurement
+    const char* const shape = std::getenv("QRK_LMPAR_CONTROL");
+    const bool last_arriver = shape && !std::strcmp(shape, "last");
+    QRK_HIP(h, qrk::launch_bd_lmpar_device(make_geom(p), p->max_cols, r_vals, perm, y, diag, delta, par, x, iters, trace, p->d_lm_scratch,
+                                           last_arriver, h->stream));
     return QRK_STATUS_OK;
 }
 

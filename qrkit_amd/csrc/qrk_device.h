@@ -254,6 +254,25 @@ hipError_t launch_bd_lm_gradient(const TileGeom& g, int max_cols, const double* 
                                  const double* diag, double* gout, double* partials, double* gnorm2, hipStream_t stream);
 hipError_t launch_bd_r_col_norms(const TileGeom& g, int max_cols, const double* r_vals, const int32_t* perm, double* norms,
                                  hipStream_t stream);
+// The control block of the device-side lmpar: the state MINPACK's loop carries from one evaluation to the next.
+// Cleared on the stream at the start of every call; written by lane 0 of bd_lm_control_kernel, read by the *_ctl_kernel solves.
+struct LmControl {
+    double par;          // of the next damped evaluation
+    double parl, paru;   // the bounds
+    double fp;           // || D x || - delta of the last evaluation
+    double delta;        // the radius as read at evaluation 0
+    double gnorm;        // || D^-1 g ||
+    int32_t evals;       // evaluations run so far = the pass number of the next one
+    int32_t done;        // nonzero: the search has stopped; every later kernel of the chain returns at once
+    uint32_t arrived[12]; // [pass]: workgroups of damped evaluation `pass` that have stored their partials (the last one to arrive does
+                         // the sums and the control step; nobody waits on it)
+};
+// The plan's LM scratch: the partials, the four sums (s0, s1, s2, gnorm2), the control block
+constexpr int BD_LM_SCRATCH_DOUBLES = 3 * BD_LM_MAX_BLOCKS + 4 + (int)(sizeof(LmControl) / sizeof(double));
+// All of delta, par (in: start value, out: result), iters (may be null) and trace (3 x 11, may be null) are device pointers
+hipError_t launch_bd_lmpar_device(const TileGeom& g, int max_cols, const double* r_vals, const int32_t* perm, const double* y,
+                                  const double* diag, const double* delta, double* par, double* x, int32_t* iters, double* trace,
+                                  double* scratch, bool last_arriver, hipStream_t stream);
 
 // ---- decision margins of the fast kernels ------------------------------------------------
 // A fast kernel (FMA chains, squared column norms, un-normalised reflector) takes a data-dependent decision of the reference

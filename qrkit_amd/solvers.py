@@ -571,6 +571,51 @@ class BlockDiagonalSparseQR:
         out = (pv.value, x.cpu().numpy() if was_np else x, it.value)
         return out + (np.array(trace[:3 * (it.value + 1)]).reshape(-1, 3),) if returnTrace else out
 
+    def _lm_scalar(self, v, what):
+        """`v` as a one-element float64 device tensor: a tensor is used in place, a float is uploaded on the current stream"""
+        if isinstance(v, torch.Tensor):
+            assert v.is_cuda and v.dtype == torch.float64 and v.numel() == 1 and v.is_contiguous(), \
+                f"{what}: expected a one-element float64 device tensor"
+            return v
+        return torch.tensor([float(v)], dtype=torch.float64).to(self._ctx.device)
+
+    def lmparDevice(self, qtb, diag, delta, par=0.0, out=None, returnTrace: bool = False):
+        """lmpar() as one enqueue (qrk_bd_lmpar_device): the same search, its scalar steps run on the device.  Returns DEVICE tensors
+        (par, x, iters) -- one float64, cols() float64, one int32 -- plus trace, (11, 3) float64 with the rows of evaluations that did
+        not run zero, when asked; it does not synchronise: read them (.item(), .cpu()) when the step is needed.
+
+        delta and par may be floats (uploaded on the current stream) or one-element float64 device tensors, which are used in
+        place: par is then overwritten with the result.  out = (par, x, iters, trace) are preallocated device tensors for the
+        results (trace may be None unless returnTrace; out[0] is also where the start value is read from, after `par` has been
+        copied into it unless `par` is that tensor): with them, and qtb / diag / delta device tensors, a torch.cuda.graph capture of
+        this call reads and writes only memory the caller keeps.  The first call on a plan allocates its scratch and must not be
+        captured.  A delta <= 0 or par < 0 (or NaN) can only be seen on the device: iters is then -1, par unchanged, x meaningless."""
+        assert self.m_isInitialized, "The factorization should be called first, use compute()"
+        y, _ = self._lm_vec(qtb, "qtb")
+        d = self._lm_diag(diag)
+        dev = self._ctx.device
+        dl = self._lm_scalar(delta, "delta")
+        if out is not None:
+            pv, x, it, trace = out
+            assert x.is_cuda and x.dtype == torch.float64 and x.is_contiguous() and x.numel() >= max(self._cols, 1), "out: x"
+            assert it.is_cuda and it.dtype == torch.int32 and it.numel() == 1, "out: iters"
+            assert trace is None or (trace.is_cuda and trace.dtype == torch.float64 and trace.is_contiguous() and trace.numel() == 33), "out: trace"
+            assert trace is not None or not returnTrace, "out: returnTrace needs a trace tensor"
+            self._lm_scalar(pv, "out: par")
+            if not (isinstance(par, torch.Tensor) and par.data_ptr() == pv.data_ptr()):
+                pv.copy_(self._lm_scalar(par, "par").reshape(pv.shape))
+        else:
+            pv = self._lm_scalar(par, "par")
+            x = torch.empty(max(self._cols, 1), dtype=torch.float64, device=dev)
+            it = torch.empty(1, dtype=torch.int32, device=dev)
+            trace = torch.empty((11, 3), dtype=torch.float64, device=dev) if returnTrace else None
+        self._ctx.use_current_stream()
+        capi.check(capi.lib().qrk_bd_lmpar_device(self._plan, self._r.data_ptr(), self._perm.data_ptr(), y.data_ptr(),
+                                                  d.data_ptr() if d is not None else None, dl.data_ptr(), pv.data_ptr(), x.data_ptr(),
+                                                  it.data_ptr(), trace.data_ptr() if trace is not None else None), self._ctx.handle)
+        res = (pv, x[:self._cols], it)
+        return res + (trace.reshape(11, 3),) if returnTrace else res
+
     # -- helpers ---------------------------------------------------------------------------
     def _rhs(self, B, n):
         was_np = not isinstance(B, torch.Tensor)
