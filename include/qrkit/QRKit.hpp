@@ -598,6 +598,26 @@ class BlockDiagonalSparseQR {
         check(qrk_bd_solve_r(m_plan, (const double*)m_dr, d_y, nrhs, d_z, QRK_MEM_DEVICE));
         check(qrk_synchronize(m_handle));
     }
+    // The reflectors of the damped solve over a device panel (qrk_bd_lm_panel on this solver's R and permutation; include/qrkit_amd.h
+    // has the layout of every argument), and the triangular step with damped factors d_s in R's packed layout.  Device pointers;
+    // they return when the result is in memory.  BlockAngularSparseQR::lmSolve is built on them.
+    void lmPanelDevice(const double* d_diag, double par, const double* d_c, int64_t ldc, int64_t ncols, const int32_t* d_colidx,
+                       double* d_s, double* d_top, int64_t ldt, double* d_fill, int64_t ldf) const {
+        assert(m_isInitialized && "The factorization should be called first, use compute()");
+        check(qrk_bd_lm_panel(m_plan, (const double*)m_dr, (const int32_t*)m_dperm, d_diag, par, d_c, ldc, ncols, d_colidx, d_s, d_top, ldt,
+                              d_fill, ldf));
+        check(qrk_synchronize(m_handle));
+    }
+    void solveDampedDevice(const double* d_s, const double* d_y, int64_t nrhs, double* d_z) const {
+        check(qrk_bd_solve_r(m_plan, d_s, d_y, nrhs, d_z, QRK_MEM_DEVICE));
+        check(qrk_synchronize(m_handle));
+    }
+    // the kernel lmPanelDevice() runs on this plan; contains "unsupported" where it would refuse
+    std::string lmPanelKernelName(int64_t ncols = 1) const {
+        assert(m_analysisIsok && "analyzePattern() should be called first");
+        return std::string(qrk_bd_lm_panel_kernel_name(m_plan, ncols));
+    }
+    int64_t nonZerosR() const { return m_nr; }
 
   protected:
     void check(qrk_status st) const {
@@ -1528,6 +1548,11 @@ class BlockAngularSparseQR {
     }
     ~BlockAngularSparseQR() {
         m_dense.release();
+        m_lmDense.release();
+        if (m_lmTop.p) qrk_device_free(m_handle, m_lmTop.p);
+        if (m_lmG.p) qrk_device_free(m_handle, m_lmG.p);
+        if (m_lmS.p) qrk_device_free(m_handle, m_lmS.p);
+        if (m_lmIdx.p) qrk_device_free(m_handle, m_lmIdx.p);
         if (m_dS) qrk_device_free(m_handle, m_dS);
         if (m_dTop.p) qrk_device_free(m_handle, m_dTop.p);
         if (m_dT.p) qrk_device_free(m_handle, m_dT.p);
@@ -1677,6 +1702,60 @@ class BlockAngularSparseQR {
     }
     bool hasQ() const { return !m_qless; }
 
+    // x = argmin || J x - b ||^2 + par || D x ||^2 on the factors the last factorizeAndSolve() / computeAndSolve() left on the device
+    // (the damped solve MINPACK's lmpar repeats for every trial par, examples/ellipse_fitting.cpp:257-280): nothing is re-factorised,
+    // no Q is read, W is not modified -- the call can be repeated with any par >= 0, and matrixR() etc. keep working.  diag: cols()
+    // positive scale factors in J's column order (left part first), null = ones; *dxnorm2 (when asked) = || D x ||^2 of the returned x.
+    // qrk_bd_lm_panel triangularises [R1; sqrt(par) D1] tile by tile and takes the reflectors over W(0:m1, [P2, m2]); the fill lands
+    // in the right stack G = [R2 y2; fill; sqrt(par) D2(P2) 0] (qrk_dense_lm_stack writes the other rows), G(:, 0:m2) is factorised
+    // without pivoting, Q^T goes over its last column, and the back substitution is factorizeAndSolve()'s with the damped factors.
+    // The work arrays and the dense plan are kept between calls of one shape.  The dense factorisation of G synchronises the stream
+    // when (m1 + 2 m2) * m2 >= 2^18 (qrk_dense_factorize); this facade waits for every step in any case.
+    // Throws before a factorizeAndSolve() / computeAndSolve() that took the fused route (rows - m1 >= m2).
+    Vector lmSolve(const Vector* diag, double par, double* dxnorm2 = 0) {
+        if (!(m_isInitialized && m_qless && m_lmReady))
+            throw std::runtime_error("qrkit: lmSolve(): no kept factors; call factorizeAndSolve() or computeAndSolve() first (with rows - m1 >= m2)");
+        if (!(par >= 0.0)) throw std::invalid_argument("qrkit: lmSolve(): par must be >= 0");
+        if (diag && (Index)diag->size() != m_cols) throw std::invalid_argument("qrkit: diag must have cols() entries");
+        const int64_t D = (int64_t)sizeof(double);
+        const Index m1 = m_m1, m2 = m_m2, ldg = m1 + 2 * m2;
+        m_lmTop.reserve(*this, m1 * (m2 + 1)); m_lmG.reserve(*this, ldg * (m2 + 1));
+        m_lmS.reserve(*this, m_leftSolver.nonZerosR()); m_lmIdx.reserve(*this, (m2 + 2) / 2 + 1);
+        double *W = m_dW.ptr(), *top = m_lmTop.ptr(), *G = m_lmG.ptr(), *S = m_lmS.ptr();
+        int32_t* colidx = (int32_t*)m_lmIdx.p;
+        std::vector<int32_t> idx((size_t)(m2 + 1));
+        for (Index j = 0; j < m2; ++j) idx[(size_t)j] = (int32_t)m_P2[(size_t)j];
+        idx[(size_t)m2] = (int32_t)m2;
+        check(qrk_memcpy(m_handle, colidx, idx.data(), (m2 + 1) * (int64_t)sizeof(int32_t), 0));
+        DBuf dd(*this, m_cols);
+        if (diag) check(qrk_memcpy(m_handle, dd.p, diag->data(), m_cols * D, 0));
+        const double* d1 = diag ? dd.ptr() : (const double*)0;
+        m_leftSolver.lmPanelDevice(d1, par, W, m_rows, m2 + 1, colidx, S, top, m1, G + m2, ldg);
+        check(qrk_dense_lm_stack(m_handle, W + m1, m_rows, (int32_t)m2, W + m2 * m_rows + m1, diag ? dd.ptr() + m1 : (const double*)0,
+                                 m_dense.permDevice(), par, m1, G, ldg));
+        std::vector<double> hc;
+        std::vector<int32_t> pg;
+        m_lmDense.factorizeDeviceView(m_handle, G, ldg, ldg, m2, (int)QRK_HOUSEHOLDER, hc, pg);
+        m_lmDense.applyQDevice(G + m2 * ldg, 1, true);
+        DBuf z2(*this, m2), y1(*this, m1), z1(*this, m1);
+        check(qrk_memcpy_2d(m_handle, z2.p, m2 * D, G + m2 * ldg, m2 * D, m2 * D, 1, 2));
+        check(qrk_memcpy_2d(m_handle, y1.p, m1 * D, top + m2 * m1, m1 * D, m1 * D, 1, 2));
+        m_lmDense.solveRDevice(z2.ptr(), m2, 1);
+        check(qrk_dense_gemv_sub(m_handle, top, m1, m1, m2, (const int32_t*)0, z2.ptr(), y1.ptr()));
+        check(qrk_synchronize(m_handle));
+        m_leftSolver.solveDampedDevice(S, y1.ptr(), 1, z1.ptr());
+        Vector z((size_t)(m1 + m2));
+        check(qrk_memcpy(m_handle, z.data(), z1.p, m1 * D, 1));
+        check(qrk_memcpy(m_handle, z.data() + m1, z2.p, m2 * D, 1));
+        Vector x = m_outputPerm_c * z;
+        if (dxnorm2) {
+            double s = 0.0;
+            for (size_t j = 0; j < x.size(); ++j) { const double v = (diag ? (*diag)[j] : 1.0) * x[j]; s += v * v; }
+            *dxnorm2 = s;
+        }
+        return x;
+    }
+
     Index rows() const { return m_rows; }
     Index cols() const { return m_cols; }
     Index rank() const { assert(m_isInitialized); return m_nonzeropivots; }
@@ -1721,7 +1800,7 @@ class BlockAngularSparseQR {
     template <typename LeftMat, typename TopFn, typename BottomFn>
     void factorizeWith(const LeftMat& left, Index m2, TopFn top, BottomFn bottom) {
         m_m1 = left.cols(); m_n1 = left.rows(); m_m2 = m2;
-        m_isInitialized = false; m_Rbuilt = false; m_qless = false;
+        m_isInitialized = false; m_Rbuilt = false; m_qless = false; m_lmReady = false;
         // J1 = Q1 R1 (:472-475)
         m_leftSolver.compute(left);
         m_info = m_leftSolver.info();
@@ -1769,7 +1848,7 @@ class BlockAngularSparseQR {
     Vector fusedStep(const LeftMat& left, Index m2, const Vector& b, Vector* QtB, FillFn fill) {
         assert((Index)b.size() == m_rows && "SparseQR::solve() : invalid number of rows in the right hand side matrix");
         m_m1 = left.cols(); m_n1 = left.rows(); m_m2 = m2;
-        m_isInitialized = false; m_Rbuilt = false; m_qless = true;
+        m_isInitialized = false; m_Rbuilt = false; m_qless = true; m_lmReady = false;
         const int64_t D = (int64_t)sizeof(double);
         const Index rb = m_rows - m_m1;
         m_leftSolver.analyzePattern(left);
@@ -1800,6 +1879,7 @@ class BlockAngularSparseQR {
         m_P2.assign(p2.begin(), p2.begin() + m_m2);
         m_nonzeropivots = m_leftSolver.rank() + m_k2;
         m_isInitialized = true;
+        m_lmReady = true;
         // _solve_impl (:202-227) on y = Q^T b = W(:, m2): z2 = R2^-1 y2, y1 -= S(:, P2) z2, z1 = R1^-1 y1
         const double* y = W + m2 * m_rows;
         if (QtB) { QtB->assign((size_t)m_rows, 0.0); check(qrk_memcpy(m_handle, QtB->data(), y, m_rows * D, 1)); }
@@ -1913,6 +1993,9 @@ class BlockAngularSparseQR {
     const double* m_strip = 0;          // the strip as the back substitution reads it: m_dS (leading dimension m1) or W (rows)
     Index m_stripLd = 0;
     bool m_qless = false;               // the last factorisation was factorizeAndSolve()
+    bool m_lmReady = false;             // ... and took the fused route: W holds the factors lmSolve() works on
+    Scratch m_lmTop, m_lmG, m_lmS, m_lmIdx;   // device: top panel, right stack, damped left factors, column indices of lmSolve(), kept between calls
+    DenseDeviceQR m_lmDense;            // the un-pivoted factorisation of the right stack
     std::vector<double> m_hc;
     std::vector<int> m_P2;
     mutable MatrixRType m_R;            // host copy of R, assembled by the first matrixR()

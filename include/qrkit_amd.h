@@ -336,6 +336,41 @@ qrk_status qrk_bd_lmpar_device(qrk_bd_plan plan, const double* r_vals, const int
  * pointer is static, like qrk_bd_kernel_name. */
 const char* qrk_bd_lm_kernel_name(qrk_bd_plan plan);
 
+/* The reflectors of the damped solve applied to a PANEL: the left half of the damped solve on the factors the block-angular solver
+ * keeps (BlockAngularSparseQR.h:459-514).  Per tile t (c columns, first column base_col, Dt = diag in the tile's
+ * pivoted order) the stack [R_t; sqrt(par) Dt] is triangularised by qrk_bd_lm_solve's reflectors and the same reflectors go over the
+ * tile's rows of the panel stacked on c zero rows:
+ *     H [R_t  C_t; sqrt(par) Dt  0] = [S_t  top_t; 0  fill_t],     S_t^T S_t = R_t^T R_t + par Dt^2
+ * DEVICE pointers only; enqueue-only on the handle's stream: no synchronisation, no allocation.
+ *   r_vals, perm, diag                 in  : as for qrk_bd_lm_solve (diag in the matrix's own column order; NULL = all ones)
+ *   c, ldc, ncols, colidx              in  : panel column j is c + colidx[j] ldc (c + j ldc when colidx is NULL), mat_cols rows, tile
+ *                                            t's rows at its base_col; ldc >= mat_cols; ncols >= 0
+ *   s_vals [nnz_r]                     out : the packed S_t in r_vals' layout (what qrk_bd_solve_r takes)
+ *   top, ldt / fill, ldf               out : column j at top + j ldt / fill + j ldf, mat_cols rows each (ldt, ldf >= mat_cols); the rows
+ *                                            beyond mat_cols of a column are not touched
+ * With ncols = 0 only s_vals is written (c, top and fill may be NULL).  Output spans must not overlap the inputs.
+ * Plan support is that of qrk_bd_lm_solve (QRK_STATUS_UNSUPPORTED otherwise); a NULL plan / r_vals / perm / s_vals, NULL panel
+ * pointers with ncols > 0, par < 0 or NaN are QRK_STATUS_INVALID_ARGUMENT before a device is touched.
+ * par = 0 makes every reflector the identity: s_vals = r_vals, top = the gathered panel, fill = +0.0, bit for bit.  No atomics; the
+ * grid is a function of the plan and ncols: two identical calls give identical bits. */
+qrk_status qrk_bd_lm_panel(qrk_bd_plan plan, const double* r_vals, const int32_t* perm, const double* diag, double par,
+                           const double* c, int64_t ldc, int64_t ncols, const int32_t* colidx,
+                           double* s_vals, double* top, int64_t ldt, double* fill, int64_t ldf);
+
+/* Name of the kernel qrk_bd_lm_panel runs on this plan, or a string that contains "unsupported" where it would refuse ("" for a
+ * NULL plan).  The pointer is static. */
+const char* qrk_bd_lm_panel_kernel_name(qrk_bd_plan plan, int64_t ncols);
+
+/* The 2 m2 rows of the right stack G of the block-angular damped solve that qrk_bd_lm_panel does not write.  G is (m2 + m1 + m2) x
+ * (m2 + 1), column-major with leading dimension ldg; rows m2 .. m2 + m1 are the panel's fill (qrk_bd_lm_panel writes it there).
+ *   rows 0 .. m2        : [triu(qr) | y2] -- qr is the packed QR of the right block (m2 columns, leading dimension lda): the
+ *                         reflectors below the diagonal are not copied, the rows below it are zero
+ *   rows m2 + m1 ..     : sqrt(par) diag2[perm2[k]] on the diagonal (diag2 NULL = ones, perm2 NULL = identity), zero elsewhere, the
+ *                         last column included
+ * DEVICE pointers, enqueue-only on the handle's stream.  m2 = 0 writes nothing. */
+qrk_status qrk_dense_lm_stack(qrk_handle h, const double* qr, int64_t lda, int32_t m2, const double* y2,
+                              const double* diag2, const int32_t* perm2, double par, int64_t m1, double* g, int64_t ldg);
+
 /* --------------------------------------------- dense right-block solver (angular) */
 
 /* A single dense Householder QR with implicit Q: the _BlockQRSolverRight of

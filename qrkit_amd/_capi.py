@@ -34,6 +34,7 @@ EXPORTS = (
     "qrk_bd_factorize_rhs", "qrk_bd_rhs_kernel_name",
     "qrk_bd_factorize_apply_qt", "qrk_bd_panel_kernel_name",
     "qrk_bd_lm_solve", "qrk_bd_lm_gradient", "qrk_bd_r_col_norms", "qrk_bd_lmpar", "qrk_bd_lmpar_device", "qrk_bd_lm_kernel_name",
+    "qrk_bd_lm_panel", "qrk_bd_lm_panel_kernel_name", "qrk_dense_lm_stack",
 )
 
 
@@ -124,6 +125,12 @@ def lib() -> C.CDLL:
     L.qrk_bd_lmpar_device.argtypes = [vp, dp, ip, dp, dp, dp, dp, dp, ip, dp]
     L.qrk_bd_lm_kernel_name.restype = C.c_char_p
     L.qrk_bd_lm_kernel_name.argtypes = [vp]
+    L.qrk_bd_lm_panel.restype = C.c_int
+    L.qrk_bd_lm_panel.argtypes = [vp, dp, ip, dp, C.c_double, dp, C.c_int64, C.c_int64, ip, dp, dp, C.c_int64, dp, C.c_int64]
+    L.qrk_bd_lm_panel_kernel_name.restype = C.c_char_p
+    L.qrk_bd_lm_panel_kernel_name.argtypes = [vp, C.c_int64]
+    L.qrk_dense_lm_stack.restype = C.c_int
+    L.qrk_dense_lm_stack.argtypes = [vp, dp, C.c_int64, C.c_int32, dp, dp, ip, C.c_double, C.c_int64, dp, C.c_int64]
     L.qrk_dense_plan_create.restype = C.c_int
     L.qrk_dense_plan_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int, C.POINTER(vp)]
     L.qrk_dense_plan_destroy.restype = C.c_int

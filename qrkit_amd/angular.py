@@ -434,6 +434,9 @@ class BlockAngularSparseQR:
         self.m_isInitialized = False
         self._qless = False          # the last factorisation was factorizeAndSolve(): Q1 was never formed
         self._W = self._Win = None   # rows x (m2 + 1) work matrices of factorizeAndSolve(), kept between calls of one shape
+        self._lm_ready = False       # factorizeAndSolve() took the fused route: W holds the factors lmSolve() works on
+        self._lm_np = True           # ... and b was a numpy array
+        self._lm = None              # work arrays and dense plan of lmSolve(), kept between calls of one shape
 
     def compute(self, mat: BlockMatrix1x2):
         self.analyzePattern(mat)
@@ -463,6 +466,7 @@ class BlockAngularSparseQR:
         was_np = not isinstance(b, torch.Tensor)
         bt = (torch.as_tensor(np.asarray(b, dtype=np.float64)) if was_np else b).reshape(-1)
         assert bt.shape[0] == rows, "SparseQR::solve() : invalid number of rows in the right hand side matrix"
+        self._lm_ready = False
         if rows - m1 < m2:
             self.factorize(mat)
             x = self.solve(b)
@@ -509,10 +513,78 @@ class BlockAngularSparseQR:
         z1 = self.m_leftSolver.solveR(rhs1)
         x = torch.empty(m1 + m2, dtype=torch.float64, device=dev)
         x[self.m_outputPerm_c.long()] = torch.cat([z1.reshape(-1), z2.reshape(-1)])
+        self._lm_ready, self._lm_np = True, was_np
         if was_np:
             x = x.cpu().numpy()
             qtb = qtb.cpu().numpy() if returnQtB else None
         return (x, qtb) if returnQtB else x
+
+    def lmSolve(self, diag, par: float, returnDxNorm2: bool = False):
+        """x = argmin || J x - b ||^2 + par || D x ||^2 on the factors the last factorizeAndSolve() / computeAndSolve() left on
+        the device (the damped solve MINPACK's lmpar repeats for every trial par, examples/ellipse_fitting.cpp:257-280): nothing
+        is re-factorised, no Q is read, W is not modified -- the call can be repeated with any par >= 0, and matrixR() etc. keep
+        working.  diag: cols() positive scale factors in J's column order (left part first), None = ones.
+
+        qrk_bd_lm_panel triangularises [R1; sqrt(par) D1] tile by tile and takes the reflectors over W(0:m1, [P2, m2]): the
+        damped left factors, the top panel and the fill, which lands in the right stack G = [R2 y2; fill; sqrt(par) D2(P2) 0]
+        (qrk_dense_lm_stack writes the other rows); G(:, 0:m2) is factorised without pivoting (Householder dense plan), Q^T
+        goes over its last column, and the back substitution is factorizeAndSolve()'s with the damped factors.  The work
+        arrays and the dense plan are kept between calls of one shape.
+
+        Returns x in J's column order, numpy or tensor as `b` was given to factorizeAndSolve(); with returnDxNorm2 also
+        || D x ||^2 (a float, from the returned x).  The dense factorisation of G synchronises the stream when
+        (m1 + 2 m2) * m2 >= 2^18 (qrk_dense_factorize): the call cannot be captured into a graph at those sizes.
+        Raises before a factorizeAndSolve() / computeAndSolve() that took the fused route (rows - m1 >= m2)."""
+        if not (self.m_isInitialized and self._qless and self._lm_ready):
+            raise RuntimeError("lmSolve(): no kept factors; call factorizeAndSolve() or computeAndSolve() first "
+                               "(with rows - m1 >= m2: the explicit route keeps none)")
+        par = float(par)
+        if not par >= 0.0:
+            raise ValueError("lmSolve(): par must be >= 0")
+        dev = self._ctx.device
+        m1, m2, rows, W = self._m1, self._m2, self._rows, self._W
+        left = self.m_leftSolver
+        d = None
+        if diag is not None:
+            d = (torch.as_tensor(np.asarray(diag, dtype=np.float64)) if not isinstance(diag, torch.Tensor) else diag)
+            d = d.reshape(-1).to(dev, torch.float64).contiguous()
+            assert d.numel() == m1 + m2, "diag: expected cols() entries"
+        ldg = m1 + 2 * m2
+        lm = self._lm
+        if lm is None or lm["key"] != (m1, m2, left._nnz_r):
+            lm = self._lm = {
+                "key": (m1, m2, left._nnz_r),
+                "top": torch.empty(m2 + 1, max(m1, 1), dtype=torch.float64, device=dev).t(),      # column-major m1 x (m2 + 1)
+                "G": torch.empty(m2 + 1, ldg, dtype=torch.float64, device=dev).t(),              # column-major ldg x (m2 + 1)
+                "s": torch.empty(max(left._nnz_r, 1), dtype=torch.float64, device=dev),
+                "dense": DenseColPivQR(self._ctx, capi.HOUSEHOLDER),
+                "colidx": torch.empty(m2 + 1, dtype=torch.int32, device=dev),
+            }
+        top, G, s_vals, colidx = lm["top"], lm["G"], lm["s"], lm["colidx"]
+        p2 = self.m_rightSolver.colsPermutation()
+        colidx[:m2].copy_(p2)
+        colidx[m2] = m2
+        L, h = capi.lib(), self._ctx.handle
+        self._ctx.use_current_stream()
+        capi.check(L.qrk_bd_lm_panel(left._plan, left._r.data_ptr(), left._perm.data_ptr(), d.data_ptr() if d is not None else None,
+                                     par, W.data_ptr(), rows, m2 + 1, colidx.data_ptr(), s_vals.data_ptr(), top.data_ptr(), max(m1, 1),
+                                     G.data_ptr() + 8 * m2, ldg), h)
+        capi.check(L.qrk_dense_lm_stack(h, W.data_ptr() + 8 * m1, rows, m2, W.data_ptr() + 8 * (m2 * rows + m1),
+                                        d[m1:].data_ptr() if d is not None else None, p2.data_ptr(), par, m1, G.data_ptr(), ldg), h)
+        dense = lm["dense"].compute(G[:, :m2])
+        dense.applyQ(G[:, m2:], transpose=True)
+        z2 = dense.solveR(G[:m2, m2].clone().reshape(m2, 1))
+        rhs1 = top[:, m2].clone().reshape(m1, 1)
+        capi.check(L.qrk_dense_gemv_sub(h, top.data_ptr(), max(m1, 1), m1, m2, None, z2.data_ptr(), rhs1.data_ptr()), h)
+        z1 = torch.empty_like(rhs1)
+        capi.check(L.qrk_bd_solve_r(left._plan, s_vals.data_ptr(), rhs1.data_ptr(), 1, z1.data_ptr(), capi.MEM_DEVICE), h)
+        x = torch.empty(m1 + m2, dtype=torch.float64, device=dev)
+        x[self.m_outputPerm_c.long()] = torch.cat([z1.reshape(-1), z2.reshape(-1)])
+        dx2 = None
+        if returnDxNorm2:
+            dx2 = float(torch.sum((x * d) ** 2 if d is not None else x ** 2).item())
+        xo = x.cpu().numpy() if self._lm_np else x
+        return (xo, dx2) if returnDxNorm2 else xo
 
     def _need_q(self, what: str):
         if self._qless:
@@ -533,6 +605,7 @@ class BlockAngularSparseQR:
         m2 = int(right.shape[1])
         n2 = int(right.shape[0]) - n1
         self._qless = False
+        self._lm_ready = False
         # J1 = Q1 R1 (:472-475)
         self.m_leftSolver.compute(left)
         assert self.m_leftSolver.info() == capi.INFO_SUCCESS

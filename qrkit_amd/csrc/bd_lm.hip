@@ -20,50 +20,10 @@
 // The sums are deterministic: every workgroup adds its lanes in a fixed order into one partial per sum (a scratch the plan owns),
 // a one-workgroup pass adds the partials in a fixed order; no floating-point atomics; the grid is a function of the plan.
 #include "qrk_device.h"
+#include "bd_lm_geom.h"     // LmGeom, lm_geom, lm_reflector, THREADS: shared with bd_lm_panel.hip
 
 namespace qrk {
 namespace lm {
-
-constexpr int THREADS = 256;
-
-// What these kernels need of a TileGeom (kernel arguments live in scalar registers for the whole kernel: 9 instead of 26)
-struct LmGeom {
-    int64_t num_tiles;
-    const int32_t* t_cols;       // null: uniform tiles of `cols` columns
-    const int64_t* r_off;
-    const int32_t* c_off;
-    int32_t cols;
-};
-
-static LmGeom lm_geom_of(const TileGeom& g)
-{
-    LmGeom l{};
-    l.num_tiles = g.num_tiles; l.cols = g.cols;
-    l.t_cols = g.t_rows ? g.t_cols : nullptr; l.r_off = g.r_off; l.c_off = g.c_off;
-    return l;
-}
-
-__device__ __forceinline__ void lm_geom(const LmGeom& g, int64_t t, int& c, int64_t& roff, int& base_col)
-{
-    if (g.t_cols) {
-        c = g.t_cols[t]; roff = g.r_off[t]; base_col = g.c_off[t];
-    } else {
-        c = g.cols; roff = t * (int64_t)(c * (c + 1) / 2); base_col = (int)(t * c);
-    }
-}
-
-// Reflector of the column [a; l], sigma = |l|^2: beta = the new diagonal entry, v0 = a - beta (no cancellation: beta has the sign
-// of -a), gm = 1 / (v^T v / 2).  sigma = 0 (par = 0, or nothing below): the identity, written as gm = v0 = 0.
-__device__ __forceinline__ void lm_reflector(double a, double sigma, double& beta, double& v0, double& gm)
-{
-    if (sigma > 0.0) {
-        beta = -copysign(sqrt(fma(a, a, sigma)), a);
-        v0 = a - beta;
-        gm = -1.0 / (beta * v0);
-    } else {
-        beta = a; v0 = 0.0; gm = 0.0;
-    }
-}
 
 // Sum of v[n] over the 256 threads of the workgroup in a fixed order: xor butterfly inside every wavefront (the same bits in all of
 // its lanes), then the four wavefronts in order.  red: 4 N doubles of LDS.

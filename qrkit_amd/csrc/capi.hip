@@ -1519,6 +1519,47 @@ const char* qrk_bd_lm_kernel_name(qrk_bd_plan p)
     }
 }
 
+qrk_status qrk_bd_lm_panel(qrk_bd_plan p, const double* r_vals, const int32_t* perm, const double* diag, double par, const double* c,
+                           int64_t ldc, int64_t ncols, const int32_t* colidx, double* s_vals, double* top, int64_t ldt, double* fill,
+                           int64_t ldf)
+{
+    if (!p || !r_vals || !perm || !s_vals || !(par >= 0.0) || ncols < 0 ||
+        (ncols > 0 && (!c || !top || !fill || ldc < p->mat_cols || ldt < p->mat_cols || ldf < p->mat_cols)))
+        return fail(p ? p->h : nullptr, QRK_STATUS_INVALID_ARGUMENT,
+                    "qrk_bd_lm_panel: bad argument (NULL buffer, par < 0 or NaN, ncols < 0, or a leading dimension below mat_cols)");
+    qrk_handle h = p->h;
+    if (const char* why = lm_unsupported(p)) return fail(h, QRK_STATUS_UNSUPPORTED, std::string("qrk_bd_lm_panel: ") + why);
+    QRK_HIP(h, hipSetDevice(h->device));
+    QRK_HIP(h, qrk::launch_bd_lm_panel(make_geom(p), p->max_cols, r_vals, perm, diag, par, c, ldc, ncols, colidx, s_vals, top, ldt, fill, ldf,
+                                       h->num_cus, h->stream));
+    return QRK_STATUS_OK;
+}
+
+const char* qrk_bd_lm_panel_kernel_name(qrk_bd_plan p, int64_t ncols)
+{
+    if (!p) return "";
+    (void)ncols;     // (one kernel per plan serves every width; the width only sets the grid)
+    if (p->q_format != QRK_FULL_Q) return "unsupported: R is upper triangular only in the FullQ format";
+    switch (qrk::bd_lm_panel_cap(p->max_cols)) {
+    case 0: return "qrk::lm::bd_lm_panel_thin_kernel";
+    case 8: return "qrk::lm::bd_lm_panel_group_kernel<8>";
+    case 16: return "qrk::lm::bd_lm_panel_group_kernel<16>";
+    case 32: return "qrk::lm::bd_lm_panel_group_kernel<32>";
+    default: return "unsupported: a tile of this plan has more than 32 columns";
+    }
+}
+
+qrk_status qrk_dense_lm_stack(qrk_handle h, const double* qr, int64_t lda, int32_t m2, const double* y2, const double* diag2,
+                              const int32_t* perm2, double par, int64_t m1, double* g, int64_t ldg)
+{
+    if (!h || m2 < 0 || m1 < 0 || !(par >= 0.0) || (m2 > 0 && (!qr || !y2 || !g || lda < m2 || ldg < 2 * (int64_t)m2 + m1)))
+        return fail(h, QRK_STATUS_INVALID_ARGUMENT, "qrk_dense_lm_stack: bad argument");
+    if (m2 == 0) return QRK_STATUS_OK;
+    QRK_HIP(h, hipSetDevice(h->device));
+    QRK_HIP(h, qrk::launch_dense_lm_stack(qr, lda, m2, y2, diag2, perm2, par, m1, g, ldg, h->stream));
+    return QRK_STATUS_OK;
+}
+
 qrk_status qrk_dense_plan_create(qrk_handle h, int32_t rows, int32_t cols, qrk_block_solver solver,
                                  qrk_dense_plan* out)
 {

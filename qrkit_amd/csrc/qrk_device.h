@@ -273,6 +273,17 @@ constexpr int BD_LM_SCRATCH_DOUBLES = 3 * BD_LM_MAX_BLOCKS + 4 + (int)(sizeof(Lm
 hipError_t launch_bd_lmpar_device(const TileGeom& g, int max_cols, const double* r_vals, const int32_t* perm, const double* y,
                                   const double* diag, const double* delta, double* par, double* x, int32_t* iters, double* trace,
                                   double* scratch, bool last_arriver, hipStream_t stream);
+// bd_lm_panel.hip: the reflectors of the damped solve applied to a strided panel: s_vals = the damped factors S_t in
+// r_vals' layout, top / fill = the two halves of H [C_t; 0] at the tiles' rows.  Column j of the panel at c + (colidx ? colidx[j] : j) ldc.
+struct LmPanelGrid { int chunks, slices, cols_per_slice; };
+int bd_lm_panel_cap(int max_cols);        // 0: one lane per tile; 8 / 16 / 32 lanes per tile; -1: not supported
+LmPanelGrid bd_lm_panel_grid(int64_t num_tiles, int max_cols, int64_t ncols, int num_cus);
+hipError_t launch_bd_lm_panel(const TileGeom& g, int max_cols, const double* r_vals, const int32_t* perm, const double* diag, double par,
+                              const double* c, int64_t ldc, int64_t ncols, const int32_t* colidx, double* s_vals, double* top, int64_t ldt,
+                              double* fill, int64_t ldf, int num_cus, hipStream_t stream);
+// rows 0 .. m2 ([triu(R2) | y2]) and m2 + m1 .. ([sqrt(par) diag2(perm2) | 0]) of the right stack gs, (m2 + m1 + m2) x (m2 + 1)
+hipError_t launch_dense_lm_stack(const double* qr, int64_t lda, int m2, const double* y2, const double* diag2, const int32_t* perm2,
+                                 double par, int64_t m1, double* gs, int64_t ldg, hipStream_t stream);
 
 // ---- decision margins of the fast kernels ------------------------------------------------
 // A fast kernel (FMA chains, squared column norms, un-normalised reflector) takes a data-dependent decision of the reference
