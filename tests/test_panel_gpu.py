@@ -318,10 +318,12 @@ def test_argument_checks_and_landscape(qa, ctx):
     assert refused(ldc=n - 1) and refused(ldq=n - 1)
     assert refused(ncols=-1)
     assert refused(tiles=None) and refused(rr=None) and refused(pp=None) and refused(cc=None) and refused(yy=None)
-    assert refused(yy=c.data_ptr())                                          # the same span
-    assert refused(yy=c.data_ptr() + 8 * (2 * (n + 2) + n - 1))              # the first entry of qtc is the last of c
-    assert refused(cc=y.data_ptr() + 8 * (n + 2), ncols=2)                   # c inside the span of qtc
-    assert call(cc=y.data_ptr() + 8 * (2 * (n + 2) + n), ncols=1, yy=y.data_ptr()) == capi.STATUS_OK      # back to back: no overlap
+    # Every span below lies inside the 3 * (n + 2) = 216 doubles of the tensor it points into (n = 70, ld = 72: a panel of k columns
+    # spans (k - 1) * 72 + 70 elements), the refused ones too, although they never reach a kernel.
+    assert refused(yy=c.data_ptr())                                          # the same span: c and qtc both c[0, 214)
+    assert refused(yy=c.data_ptr() + 8 * (n - 1), ncols=1)                   # the first entry of qtc is the last of c: c[0, 70), qtc c[69, 139)
+    assert refused(cc=y.data_ptr() + 8 * (n + 2), ncols=2)                   # c inside the span of qtc: c y[72, 214), qtc y[0, 142)
+    assert call(cc=y.data_ptr() + 8 * n, ncols=1, yy=y.data_ptr()) == capi.STATUS_OK      # back to back, no overlap: qtc y[0, 70), c y[70, 140)
     assert call(cc=None, yy=None, ncols=0) == capi.STATUS_OK                 # no columns: no panel needed
     # a landscape tile: InvalidInput, as after qrk_bd_factorize
     rows, cols = np.array([4, 3], np.int32), np.array([2, 5], np.int32)

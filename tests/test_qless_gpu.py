@@ -302,7 +302,7 @@ def test_argument_checks_and_landscape(qa, ctx):
     qr.analyzePattern(mat)
     lib, dev = capi.lib(), ctx.device
     t = mat.device_tiles(dev)
-    b = torch.zeros(ref.mat_rows, dtype=torch.float64, device=dev)
+    b = torch.zeros(ref.mat_rows + 1, dtype=torch.float64, device=dev)                    # one more: the shifted qtb below stays inside b
     y, x = torch.zeros_like(b), torch.zeros(ref.mat_cols, dtype=torch.float64, device=dev)
     r = torch.zeros(30, dtype=torch.float64, device=dev)
     p = torch.zeros(ref.mat_cols, dtype=torch.int32, device=dev)
