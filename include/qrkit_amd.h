@@ -528,8 +528,16 @@ qrk_status qrk_tsqr_apply_q(qrk_tsqr_plan plan, const double* a, int64_t lda, in
  * (src/QRKit/SparseQROrdering.h:66-119), band detection and mergeBlocks
  * (src/QRKit/SparseQRUtils.h:186-253,308-385) on the CSR pattern of the matrix (HOST arrays), plus
  * the panel chain of factorize() (:457-508) as device descriptors.  Fails with
- * QRK_STATUS_INVALID_ARGUMENT where the reference itself is outside its domain (its mergeBlocks reads
- * back() of an empty vector for non-portrait strips, SparseQRUtils.h:375). */
+ * QRK_STATUS_INVALID_ARGUMENT where the reference itself is outside its domain: its mergeBlocks reads
+ * back() of an empty vector for non-portrait strips (SparseQRUtils.h:375), and its BlockYTY row layout
+ * (BlockYTY.h:152-172: numCols rows at rowIndex, numZeros rows skipped, then the rest) cannot express
+ * every panel of the chain.  Panel i >= 1 consists of `carried` = numRows(i-1) - (idxCol(i) - idxCol(i-1))
+ * rows taken over from panel i-1 followed by the numRows(i) rows of its own block, and its unclamped
+ * numZeros is z = idxRow(i) - idxCol(i) - carried.  The block's own rows land on their matrix rows only
+ * if z == 0, or z > 0 and carried >= numCols(i); any other pattern is refused (also by
+ * qrk_bb_plan_create_fixed and qrk_bb_analyze_host), because the reference computes the right R but a
+ * wrong Q on it.  For strips of ms rows and n columns stepping by s columns: ms - s >= n once there are
+ * more than two panels. */
 typedef struct qrk_bb_plan_s* qrk_bb_plan;
 
 qrk_status qrk_bb_plan_create(qrk_handle h, int32_t rows, int32_t cols, const int32_t* csr_rowptr,
@@ -565,6 +573,12 @@ qrk_status qrk_bb_analyze_host(int32_t rows, int32_t cols, const int32_t* csr_ro
  * AsBandedAsPossible::hasPermutation. */
 qrk_status qrk_bb_plan_info(qrk_bb_plan plan, int32_t* num_blocks, int64_t* nnz_r, int64_t* y_len,
                             int64_t* t_len, int32_t* has_row_perm);
+
+/* Which code qrk_bb_factorize runs on panel `panel` (0 .. num_blocks - 1) of this plan, host only: "bb_chain_kernel", or
+ * "bb_chain2_kernel ob<16|32> nr<3|4|8|16> t_<lds|global>" (block width and 64-row registers of the panel's blocked QR; T of
+ * the panels built in LDS or in place).  The environment switches QRK_BB_CHAIN_V1 and QRK_BB_T_GLOBAL are read as
+ * qrk_bb_factorize reads them.  "" for a bad argument.  The pointer is static, like qrk_bd_kernel_name. */
+const char* qrk_bb_kernel_name(qrk_bb_plan plan, int32_t panel);
 
 /* Host outputs: blocks[4*num_blocks] = (idxRow, idxCol, numRows, numCols) of m_blockInfo in order;
  * row_perm[rows] = rowsPermutation().indices(): (P*M).row(row_perm[i]) = M.row(i);

@@ -357,7 +357,31 @@ def bb_analyze(J, suggested: int = 2):
     else:
         perm = np.arange(M.shape[0], dtype=np.int32)
     blocks = block_info_from_csr(M.shape[0], M.shape[1], M.indptr, M.indices, suggested)
+    if blocks is not None:
+        err = bb_q_layout_error(blocks)
+        if err:
+            raise ValueError(err)
     return perm, blocks
+
+
+def bb_q_layout_error(blocks):
+    """Where the reference's BlockYTY row layout (BlockYTY.h:152-172: numCols rows at rowIndex, numZeros rows skipped, then the
+    rest) cannot express a panel of the chain below: the panel's rows are `carried` rows of the panel before and then the block's
+    own rows, which must land on the matrix rows they came from, rowIndex + carried + (numZeros before its clamp at 0).  That
+    holds when the unclamped numZeros is 0, or positive with carried >= numCols; otherwise Q is wrong although R is right, and
+    the product (qrk_bb_plan_create) refuses the pattern in the same way.  Returns a message, or None."""
+    for i in range(1, len(blocks)):
+        idxRow, idxCol, numRows, numCols = (int(v) for v in blocks[i - 1])
+        nRow, nCol, nRows, nCols = (int(v) for v in blocks[i])
+        colInc = nCol - idxCol
+        activeRows = numRows + nRows - colInc
+        zeros_raw = (nRow + nRows) - activeRows - nCol
+        carried = activeRows - nRows
+        ncols = max(nCols, idxCol + numCols - nCol)
+        if zeros_raw < 0 or (zeros_raw > 0 and carried < ncols):
+            return ("the reference's two-segment Q row layout cannot express panel %d: it carries %d rows over, fewer than its "
+                    "%d columns, with %d rows to skip" % (i, carried, ncols, zeros_raw))
+    return None
 
 
 def bb_factorize(J, suggested: int = 2) -> BBResult:

@@ -294,6 +294,18 @@ __device__ __forceinline__ void bb_pipe_publish(int* word, int rows_done, int* w
 // Householder vectors, partial V^T W of 8 column strips}
 __host__ __device__ constexpr int bb_qr_aux_doubles(int OB) { return OB * OB + 8 * (OB / 16) * 256; }
 
+// The instantiation of bb_panel_qr that bb_chain2_kernel runs on an m x n panel whose tallest block has `tall` rows, with
+// uni_doubles doubles of LDS for the block and its aux arrays: blocks of 32 columns when the block fits (m <= ~470), else of 16
+// (NR 16: every height up to 1 024); the pipelined chain always works in blocks of 16.  NR is the smallest that covers `tall`.
+// One place for the kernel and for qrk_bb_kernel_name.
+struct BBQrClass { int ob, nr; };
+__host__ __device__ inline BBQrClass bb_qr_class(int uni_doubles, int m, int tall, bool piped16)
+{
+    if (piped16) return BBQrClass{16, tall <= 192 ? 3 : tall <= 256 ? 4 : 16};
+    if ((int64_t)32 * (m | 1) + bb_qr_aux_doubles(32) <= (int64_t)uni_doubles) return BBQrClass{32, tall <= 192 ? 3 : tall <= 256 ? 4 : 8};
+    return BBQrClass{16, 16};
+}
+
 // Eigen::HouseholderQR of the m x n panel W (row-major, in place, packed; hCoeffs to hc), blocked two ways:
 //  - a block of OB columns lives in registers, one or two columns per wave with the rows over the lanes, and is
 //    factorised one reflector at a time (makeHouseholder + applyHouseholderOnTheLeft in the un-normalised form of
@@ -813,33 +825,26 @@ bb_chain2_kernel(const BBPanel* __restrict__ panels, int num_panels, const int32
                 tall = (lim - jb) > tall ? (lim - jb) : tall;
             }
         }
-#if QRK_BB_PIPE_OB16
         // The pipelined chain works in blocks of 16 columns (round 5): a panel publishes its final rows block by block and the next panel's
         // block b waits for the rows of column step + 16 (b + 1) columns, so the grain of the blocks is the grain of the overlap -- with
         // 32-column blocks a panel starts when the one before has done 96 of its 192 columns, with 16-column blocks after 80:
         // 0.1654 -> 0.1336 ms per strip at the BASELINE configs[2] shape although a panel ALONE is slower in blocks of 16 (twice the
         // block updates).  One workgroup alone (no partner to wait for) keeps the 32-column blocks.
-        if (pipe) {
+        const BBQrClass qc = bb_qr_class(uni_doubles, m, tall, QRK_BB_PIPE_OB16 && pipe != nullptr);
 #ifdef QRK_BB_PROF
-            if (tall <= 192) bb_panel_qr<16, 3>(W, m, n, rlim, pipe, qt); else if (tall <= 256) bb_panel_qr<16, 4>(W, m, n, rlim, pipe, qt); else bb_panel_qr<16>(W, m, n, rlim, pipe, qt);
+#define BB_PANEL_QR(OB, NR) bb_panel_qr<OB, NR>(W, m, n, rlim, pipe, qt)
 #else
-            if (tall <= 192) bb_panel_qr<16, 3>(W, m, n, rlim, pipe); else if (tall <= 256) bb_panel_qr<16, 4>(W, m, n, rlim, pipe); else bb_panel_qr<16>(W, m, n, rlim, pipe);
+#define BB_PANEL_QR(OB, NR) bb_panel_qr<OB, NR>(W, m, n, rlim, pipe)
 #endif
-        } else
-#endif
-        if ((int64_t)32 * (m | 1) + bb_qr_aux_doubles(32) <= (int64_t)uni_doubles) {
-#ifdef QRK_BB_PROF
-            if (tall <= 192) bb_panel_qr<32, 3>(W, m, n, rlim, pipe, qt); else if (tall <= 256) bb_panel_qr<32, 4>(W, m, n, rlim, pipe, qt); else bb_panel_qr<32>(W, m, n, rlim, pipe, qt);
-#else
-            if (tall <= 192) bb_panel_qr<32, 3>(W, m, n, rlim, pipe); else if (tall <= 256) bb_panel_qr<32, 4>(W, m, n, rlim, pipe); else bb_panel_qr<32>(W, m, n, rlim, pipe);
-#endif
+        if (qc.ob == 32) {
+            if (qc.nr == 3) BB_PANEL_QR(32, 3); else if (qc.nr == 4) BB_PANEL_QR(32, 4); else BB_PANEL_QR(32, 8);
         } else {
-#ifdef QRK_BB_PROF
-            bb_panel_qr<16>(W, m, n, rlim, pipe, qt);
-#else
-            bb_panel_qr<16>(W, m, n, rlim, pipe);
+#if QRK_BB_PIPE_OB16
+            if (qc.nr == 3) BB_PANEL_QR(16, 3); else if (qc.nr == 4) BB_PANEL_QR(16, 4); else
 #endif
+            BB_PANEL_QR(16, 16);
         }
+#undef BB_PANEL_QR
         __syncthreads();
         if (piped && s_pipe.aborted) break;            // (uniform: the chain was given up -- bb_pipe_wait; the host runs it again on one workgroup)
 
@@ -1219,6 +1224,9 @@ __device__ __forceinline__ int64_t bbs_res_off(const BBStrips& S, int i)
     return (int64_t)S.cols + (int64_t)i * (S.ms - S.n) + (i >= 1 ? (int64_t)(i - 1) * S.lo : 0);
 }
 
+// WIDE: panels of more than BC_CW columns (bb_chain_kernel's): the passes that hold a row of T^T or Y in registers, BC_CW columns
+// of it, go on over the columns beyond.  A variant of its own so that the code for the panels of bb_chain2_kernel stays as it is.
+template <bool WIDE>
 __global__ void __launch_bounds__(BA_THREADS)
 bb_apply_q_kernel(const BBPanel* __restrict__ panels, int num_panels, const double* __restrict__ y_vals,
                   const double* __restrict__ t_vals, int transpose, double* __restrict__ v, int64_t ldv, int64_t nrhs,
@@ -1311,6 +1319,7 @@ bb_apply_q_kernel(const BBPanel* __restrict__ panels, int num_panels, const doub
                         double d = 0.0;
 #pragma unroll
                         for (int q = 0; q < LB; ++q) { const int j = lane + 64 * q; if (j < n) d = fma(tv[rb][q], w1[j], d); }
+                        if (WIDE && i < n) for (int j = BC_CW + lane; j <= i; j += 64) d = fma(T[(int64_t)i * n + j], w1[j], d);
                         d = bb_wave_sum_dpp(d);
                         if (lane == 0 && i < n) w2[i] = d;
                     }
@@ -1361,6 +1370,7 @@ bb_apply_q_kernel(const BBPanel* __restrict__ panels, int num_panels, const doub
                 double d = 0.0;
 #pragma unroll
                 for (int q = 0; q < LB3; ++q) { const int j = lane + 64 * q; if (j < n) d = fma(yv[rb][q], w2[j], d); }
+                if (WIDE) { const int je = i < n ? i : n; for (int j = BC_CW + lane; j < je; j += 64) d = fma(Y[(int64_t)i * n + j], w2[j], d); }
                 d = bb_wave_sum_dpp(d);
                 if (lane == 0) {
                     const double val = seg[i] + d + (i < n ? w2[i] : 0.0);
@@ -1392,14 +1402,40 @@ bb_apply_q_kernel(const BBPanel* __restrict__ panels, int num_panels, const doub
 size_t bb_chain_smem(int max_act_rows, int max_ncols) { return (size_t)(max_act_rows + 2 * max_ncols + BB_WAVES) * sizeof(double); }
 size_t bb_apply_smem(int max_act_rows, int max_ncols) { return (size_t)(max_act_rows + 2 * max_ncols + BA_THREADS + max_ncols) * sizeof(double); }
 
+// LDS of the chain launch_bb_chain runs: bb_chain2_kernel's when every panel fits it (at most BC_CW columns, 1 024 rows), else 0:
+// bb_chain_kernel, which keeps its panel in global memory.  (QRK_BB_CHAIN_V1 forces the latter: lets the tests cover it.)
+static size_t bb_chain_v2_smem(int max_act_rows, int max_ncols, int* uni_doubles)
+{
+    const size_t smem2 = bb_chain2_smem(max_act_rows, uni_doubles);
+    return (max_ncols <= BC_CW && smem2 > 0 && !std::getenv("QRK_BB_CHAIN_V1")) ? smem2 : 0;
+}
+
+// The code launch_bb_chain runs on an m x n panel of a plan with these maxima (qrk_bb_kernel_name): the same three choices,
+// made by the same functions.
+const char* bb_chain_kernel_name(int max_act_rows, int max_ncols, int m, int n)
+{
+    (void)n;
+    int uni_doubles = 0, t_in_lds = 0;
+    if (bb_chain_v2_smem(max_act_rows, max_ncols, &uni_doubles) == 0) return "bb_chain_kernel";
+    (void)bb_t_smem(max_ncols, &t_in_lds);
+    const BBQrClass qc = bb_qr_class(uni_doubles, m, m, false);      // (no staircase in the CSR form: the tallest block is the panel)
+    static const char* const names[2][4] = {
+        {"bb_chain2_kernel ob32 nr3 t_global", "bb_chain2_kernel ob32 nr4 t_global", "bb_chain2_kernel ob32 nr8 t_global",
+         "bb_chain2_kernel ob16 nr16 t_global"},
+        {"bb_chain2_kernel ob32 nr3 t_lds", "bb_chain2_kernel ob32 nr4 t_lds", "bb_chain2_kernel ob32 nr8 t_lds",
+         "bb_chain2_kernel ob16 nr16 t_lds"}};
+    const int k = qc.ob == 16 ? 3 : qc.nr == 3 ? 0 : qc.nr == 4 ? 1 : 2;
+    return names[t_in_lds ? 1 : 0][k];
+}
+
 hipError_t launch_bb_chain(const BBPanel* panels, int num_panels, const int32_t* prowptr, const int32_t* pcol,
                            const int64_t* pmap, const double* vals, double* W, double* lo, double* y_vals, double* t_vals,
                            double* r_stage, const int64_t* r_src, int64_t nnz_r, double* r_vals, int max_act_rows,
                            int max_ncols, hipStream_t stream)
 {
     int t_in_lds = 0, uni_doubles = 0;
-    const size_t smem2 = bb_chain2_smem(max_act_rows, &uni_doubles);
-    if (max_ncols <= BC_CW && smem2 > 0 && !std::getenv("QRK_BB_CHAIN_V1")) {
+    const size_t smem2 = bb_chain_v2_smem(max_act_rows, max_ncols, &uni_doubles);
+    if (smem2 > 0) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(bb_chain2_kernel),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2);
         if (e != hipSuccess) return e;
@@ -1434,11 +1470,11 @@ hipError_t launch_bb_apply_q(const BBPanel* panels, int num_panels, const double
 {
     if (nrhs <= 0) return hipSuccess;
     const size_t smem = bb_apply_smem(max_act_rows, max_ncols);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(bb_apply_q_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    const auto kernel = max_ncols > BC_CW ? bb_apply_q_kernel<true> : bb_apply_q_kernel<false>;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     if (e != hipSuccess) return e;
     const unsigned grid = (unsigned)(nrhs < 1024 ? nrhs : 1024);
-    hipLaunchKernelGGL(bb_apply_q_kernel, dim3(grid), dim3(BA_THREADS), smem, stream, panels, num_panels, y_vals, t_vals,
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(BA_THREADS), smem, stream, panels, num_panels, y_vals, t_vals,
                        transpose, v, ldv, nrhs, max_act_rows, max_ncols, BBStrips{});
     return hipGetLastError();
 }
@@ -1511,11 +1547,11 @@ hipError_t launch_bbs_apply(const BBPanel* panels, int num_panels, const double*
 {
     if (nrhs <= 0) return hipSuccess;
     const size_t smem = bb_apply_smem(max_act_rows, n);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(bb_apply_q_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(bb_apply_q_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     if (e != hipSuccess) return e;
     BBStrips S{ya, full, ya_ld, full_ld, ms, n, s, lo, cols};
     const unsigned grid = (unsigned)(nrhs < 1024 ? nrhs : 1024);
-    hipLaunchKernelGGL(bb_apply_q_kernel, dim3(grid), dim3(BA_THREADS), smem, stream, panels, num_panels, y_vals, t_vals, transpose,
+    hipLaunchKernelGGL(bb_apply_q_kernel<false>, dim3(grid), dim3(BA_THREADS), smem, stream, panels, num_panels, y_vals, t_vals, transpose,
                        (double*)nullptr, (int64_t)0, nrhs, max_act_rows, n, S);
     return hipGetLastError();
 }

@@ -185,6 +185,7 @@ bool analyze_banded(int32_t rows, int32_t cols, const int32_t* rowptr, const int
     BlockInfo bi = out.blocks[0];
     int32_t activeRows = bi.numRows, numZeros = 0, row0 = bi.idxRow, ncolsJi = bi.numCols;
     int32_t lo_rows = 0, lo_cols = 0, lo_from = 0;
+    int32_t carried = 0, zerosRaw = 0;      // rows the panel takes over from the one before; numZeros before its clamp at 0
     for (size_t i = 0; i < nb; ++i) {
         bi = out.blocks[i];
         if (ncolsJi != bi.numCols) {
@@ -205,13 +206,27 @@ bool analyze_banded(int32_t rows, int32_t cols, const int32_t* rowptr, const int
         out.max_act_rows = std::max(out.max_act_rows, activeRows);
         out.max_ncols = std::max(out.max_ncols, bi.numCols);
         if (p.yrow + p.ncols + p.num_zeros + (p.act_rows - p.ncols) > rows) { err = "Q block exceeds the matrix rows"; return false; }
+        // BlockYTY (BlockYTY.h:152-172) places row l of the panel at matrix row yrow + l for l < ncols and at yrow + numZeros + l
+        // after that.  The panel's rows are `carried` rows of the panel before (the overlap triangle, which does start at yrow,
+        // and zero rows, which may sit anywhere) and then the block's own rows, which must land on the matrix rows they came
+        // from: row `carried` on bi.idxRow = yrow + carried + zerosRaw.  That holds when zerosRaw is 0 (one segment), or when
+        // it is positive and all ncols rows of the first segment are carried ones; otherwise some of the block's own rows fall
+        // into the first segment, zerosRaw rows above their place, and Q is wrong although R is right.
+        if (i > 0 && (zerosRaw < 0 || (zerosRaw > 0 && carried < p.ncols))) {
+            err = "the reference's two-segment Q row layout (BlockYTY: numCols rows, numZeros skipped, the rest) cannot express panel " +
+                  std::to_string(i) + ": it carries " + std::to_string(carried) + " rows over, fewer than its " + std::to_string(p.ncols) +
+                  " columns, with " + std::to_string(zerosRaw) + " rows to skip";
+            return false;
+        }
         out.panels.push_back(p);
         if (i + 1 < nb) {
             const BlockInfo nx = out.blocks[i + 1];
             const int32_t overlap = (bi.idxCol + bi.numCols) - nx.idxCol;
             const int32_t colInc = bi.numCols - overlap;
             activeRows = bi.numRows + nx.numRows - colInc;
-            numZeros = std::max((nx.idxRow + nx.numRows) - activeRows - nx.idxCol, 0);
+            zerosRaw = (nx.idxRow + nx.numRows) - activeRows - nx.idxCol;
+            numZeros = std::max(zerosRaw, 0);
+            carried = activeRows - nx.numRows;
             ncolsJi = nx.numCols >= overlap ? nx.numCols : overlap;
             row0 = bi.idxRow + colInc;
             lo_rows = overlap > 0 ? activeRows - nx.numRows : 0;

@@ -2964,4 +2964,11 @@ const char* qrk_bd_kernel_name(qrk_bd_plan p, int which)
     return piv ? "qrk::bdqr_pair_kernel<false, true, true>" : "qrk::bdqr_pair_kernel<false, false, true>";
 }
 
+const char* qrk_bb_kernel_name(qrk_bb_plan p, int32_t panel)
+{
+    if (!p || panel < 0 || (size_t)panel >= p->st.panels.size()) return "";
+    const qrk::BBPanel& bp = p->st.panels[(size_t)panel];
+    return qrk::bb_chain_kernel_name(p->st.max_act_rows, p->st.max_ncols, bp.act_rows, bp.ncols);
+}
+
 }  // extern "C"

@@ -212,6 +212,7 @@ hipError_t launch_dense_solve_r(const double* qr, int64_t lda, int n, double* b,
                                 int* flags = nullptr, int flags_cap = 0);
 hipError_t launch_bb_solve_r(const BBPanel* panels, int num_panels, const double* r_stage, int cols, double* v, int64_t ldv,
                              int64_t nrhs, hipStream_t stream);
+const char* bb_chain_kernel_name(int max_act_rows, int max_ncols, int m, int n);
 size_t bb_chain_smem(int max_act_rows, int max_ncols);
 size_t bb_apply_smem(int max_act_rows, int max_ncols);
 // strips form of the banded factorisation (banded.hip): stage B on the triangles stage A left
