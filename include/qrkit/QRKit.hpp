@@ -612,6 +612,22 @@ class BlockDiagonalSparseQR {
         check(qrk_bd_solve_r(m_plan, d_s, d_y, nrhs, d_z, QRK_MEM_DEVICE));
         check(qrk_synchronize(m_handle));
     }
+    // w_t = S_t^-T u_t per tile with damped factors d_s (qrk_bd_solve_rt; d_sums2: || w ||^2 and the tiles with a zero diagonal, may be
+    // null), and the gradient on device vectors (qrk_bd_lm_gradient): the left part of BlockAngularSparseQR::lmpar / lmGradient
+    void solveDampedTransposedDevice(const double* d_s, const double* d_u, double* d_w, double* d_sums2) const {
+        check(qrk_bd_solve_rt(m_plan, d_s, d_u, d_w, d_sums2));
+        check(qrk_synchronize(m_handle));
+    }
+    void lmGradientDevice(const double* d_y, const double* d_diag, double* d_g, double* d_gnorm2) const {
+        assert(m_isInitialized && "The factorization should be called first, use compute()");
+        check(qrk_bd_lm_gradient(m_plan, (const double*)m_dr, (const int32_t*)m_dperm, d_y, d_diag, d_g, d_gnorm2, QRK_MEM_DEVICE));
+        check(qrk_synchronize(m_handle));
+    }
+    // the kernel solveDampedTransposedDevice() runs on this plan; contains "unsupported" where it would refuse
+    std::string solveRtKernelName() const {
+        assert(m_analysisIsok && "analyzePattern() should be called first");
+        return std::string(qrk_bd_solve_rt_kernel_name(m_plan));
+    }
     // the kernel lmPanelDevice() runs on this plan; contains "unsupported" where it would refuse
     std::string lmPanelKernelName(int64_t ncols = 1) const {
         assert(m_analysisIsok && "analyzePattern() should be called first");
@@ -1553,6 +1569,7 @@ class BlockAngularSparseQR {
         if (m_lmG.p) qrk_device_free(m_handle, m_lmG.p);
         if (m_lmS.p) qrk_device_free(m_handle, m_lmS.p);
         if (m_lmIdx.p) qrk_device_free(m_handle, m_lmIdx.p);
+        if (m_lmWork.p) qrk_device_free(m_handle, m_lmWork.p);
         if (m_dS) qrk_device_free(m_handle, m_dS);
         if (m_dTop.p) qrk_device_free(m_handle, m_dTop.p);
         if (m_dT.p) qrk_device_free(m_handle, m_dT.p);
@@ -1713,10 +1730,85 @@ class BlockAngularSparseQR {
     // when (m1 + 2 m2) * m2 >= 2^18 (qrk_dense_factorize); this facade waits for every step in any case.
     // Throws before a factorizeAndSolve() / computeAndSolve() that took the fused route (rows - m1 >= m2).
     Vector lmSolve(const Vector* diag, double par, double* dxnorm2 = 0) {
-        if (!(m_isInitialized && m_qless && m_lmReady))
-            throw std::runtime_error("qrkit: lmSolve(): no kept factors; call factorizeAndSolve() or computeAndSolve() first (with rows - m1 >= m2)");
+        lmRequire("lmSolve()", diag);
         if (!(par >= 0.0)) throw std::invalid_argument("qrkit: lmSolve(): par must be >= 0");
+        double s[3];
+        Vector x = lmEvaluate(diag, par, false, s);
+        if (dxnorm2) *dxnorm2 = s[0];
+        return x;
+    }
+
+    // (g, *gnorm) = (J^T b in J's column order, || D^-1 g ||) from the UNDAMPED kept factors, what lmpar's upper bound needs:
+    // g = P R^^T y with R^ = [R1 Strip(:, P2); 0 R2] and y = Q^T b, so g1 = R1^T y1 (qrk_bd_lm_gradient on the left plan) and
+    // g2 = Strip(:, P2)^T y1 + R2^T y2 (qrk_dense_gemv_t on W's strip, qrk_dense_trmv_t on R2).  diag as for lmSolve().
+    Vector lmGradient(const Vector* diag = 0, double* gnorm = 0) {
+        lmRequire("lmGradient()", diag);
+        const int64_t D = (int64_t)sizeof(double);
+        const Index m1 = m_m1, m2 = m_m2;
+        double* W = m_dW.ptr();
+        const double* y1 = W + m2 * m_rows;                  // y = Q^T b = W(:, m2); R2 = the upper triangle of W(m1:, 0:m2)
+        DBuf dd(*this, m_cols), g1(*this, m1), g2(*this, m2), n2(*this, 1);
+        if (diag) check(qrk_memcpy(m_handle, dd.p, diag->data(), m_cols * D, 0));
+        m_lmWork.reserve(*this, qrk_dense_gemv_t_work(m1, m2));
+        m_leftSolver.lmGradientDevice(y1, diag ? dd.ptr() : (const double*)0, g1.ptr(), n2.ptr());
+        check(qrk_dense_gemv_t(m_handle, W, m_rows, m1, m2, m_dense.permDevice(), y1, 1.0, (const double*)0, g2.ptr(), m_lmWork.ptr()));
+        check(qrk_dense_trmv_t(m_handle, W + m1, m_rows, (int32_t)m2, y1 + m1, g2.ptr()));
+        check(qrk_synchronize(m_handle));
+        Vector g((size_t)m_cols), h2((size_t)m2);
+        double left2 = 0.0;
+        check(qrk_memcpy(m_handle, g.data(), g1.p, m1 * D, 1));      // (the left plan's permutation holds J's own column indices)
+        check(qrk_memcpy(m_handle, h2.data(), g2.p, m2 * D, 1));
+        check(qrk_memcpy(m_handle, &left2, n2.p, D, 1));
+        double right2 = 0.0;
+        for (Index k = 0; k < m2; ++k) {
+            const size_t j = (size_t)(m1 + m_P2[(size_t)k]);
+            g[j] = h2[(size_t)k];
+            const double q = g[j] / (diag ? (*diag)[j] : 1.0);
+            right2 += q * q;
+        }
+        if (gnorm) *gnorm = std::sqrt(left2 + right2);
+        return g;
+    }
+
+    // MINPACK's lmpar on the kept factors (what Eigen::LevenbergMarquardt calls between two factorisations,
+    // examples/ellipse_fitting.cpp:257-280): the step x with | || D x || - delta | <= 0.1 delta, or the Gauss-Newton step and par = 0
+    // when that lies inside the region.  A host loop: every evaluation is lmSolve()'s chain and the transposed pass behind it
+    // (w1 = S1^-T u1, w2 = Rg^-T (u2 - Top^T w1): qrk_bd_solve_rt, qrk_dense_gemv_t, qrk_dense_solve_rt), the scalar rule is
+    // qrk_lmpar_begin / qrk_lmpar_next (steps 1-5 of qrk_bd_lmpar, include/qrkit_amd.h).  par: in the start value, out the result;
+    // *iters: passes of the loop; *trace: (par, || D x ||^2, || S^-T D^2 z ||^2) of every evaluation.  x is lmSolve(diag, par)'s, bit for
+    // bit.  delta > 0, par >= 0.  Rank-deficient undamped factors are not handled: a zero on the diagonal at par = 0 throws.
+    Vector lmpar(const Vector* diag, double delta, double& par, int* iters = 0, Vector* trace = 0) {
+        lmRequire("lmpar()", diag);
+        if (!(delta > 0.0)) throw std::invalid_argument("qrkit: lmpar(): delta must be > 0");
+        if (!(par >= 0.0)) throw std::invalid_argument("qrkit: lmpar(): par must be >= 0");
+        double s[3], gnorm = 0.0;
+        Vector x = lmEvaluate(diag, 0.0, true, s);
+        if (s[2] > 0.0 || !std::isfinite(s[1]))
+            throw std::runtime_error("qrkit: lmpar(): the undamped factors have a zero on the diagonal (rank-deficient J is not supported)");
+        lmGradient(diag, &gnorm);
+        qrk_lmpar_state st;
+        int rc = qrk_lmpar_begin(&st, delta, par, s[0], s[1], 0.0, gnorm * gnorm);
+        while (rc == 1) {
+            x = lmEvaluate(diag, st.par, true, s);
+            rc = qrk_lmpar_next(&st, s[0], s[1]);
+        }
+        if (rc != 0) throw std::runtime_error("qrkit: lmpar(): the scalar rule refused its arguments");
+        par = st.par;
+        if (iters) *iters = (int)st.iters;
+        if (trace) trace->assign(st.trace, st.trace + 3 * (st.iters + 1));
+        return x;
+    }
+
+  private:
+    void lmRequire(const char* who, const Vector* diag) const {
+        if (!(m_isInitialized && m_qless && m_lmReady))
+            throw std::runtime_error(std::string("qrkit: ") + who + ": no kept factors; call factorizeAndSolve() or computeAndSolve() first (with rows - m1 >= m2)");
         if (diag && (Index)diag->size() != m_cols) throw std::invalid_argument("qrkit: diag must have cols() entries");
+    }
+    // One damped evaluation on the kept factors: lmSolve()'s chain, and with `transposed` the forward substitution with the damped
+    // factor S^ = [S1 Top; 0 Rg] behind it.  sums: s0 = || D x ||^2 (from the returned x) and, with `transposed`, s1 = || S^-T u ||^2
+    // with u = D~^2 z and the number of S1's tiles with a zero on the diagonal.
+    Vector lmEvaluate(const Vector* diag, double par, bool transposed, double* sums) {
         const int64_t D = (int64_t)sizeof(double);
         const Index m1 = m_m1, m2 = m_m2, ldg = m1 + 2 * m2;
         m_lmTop.reserve(*this, m1 * (m2 + 1)); m_lmG.reserve(*this, ldg * (m2 + 1));
@@ -1748,13 +1840,35 @@ class BlockAngularSparseQR {
         check(qrk_memcpy(m_handle, z.data(), z1.p, m1 * D, 1));
         check(qrk_memcpy(m_handle, z.data() + m1, z2.p, m2 * D, 1));
         Vector x = m_outputPerm_c * z;
-        if (dxnorm2) {
+        {
             double s = 0.0;
             for (size_t j = 0; j < x.size(); ++j) { const double v = (diag ? (*diag)[j] : 1.0) * x[j]; s += v * v; }
-            *dxnorm2 = s;
+            sums[0] = s;
         }
+        if (!transposed) return x;
+        // u = D~^2 z in the pivoted order, w1 = S1^-T u1, t = u2 - Top^T w1, w2 = Rg^-T t
+        Vector u(z);
+        if (diag)
+            for (size_t k = 0; k < u.size(); ++k) { const double dk = (*diag)[(size_t)m_outputPerm_c.indices()[k]]; u[k] *= dk * dk; }
+        DBuf du(*this, m1 + m2), w1(*this, m1), t2(*this, m2), s2(*this, 2);
+        m_lmWork.reserve(*this, qrk_dense_gemv_t_work(m1, m2));
+        check(qrk_memcpy(m_handle, du.p, u.data(), (m1 + m2) * D, 0));
+        m_leftSolver.solveDampedTransposedDevice(S, du.ptr(), w1.ptr(), s2.ptr());
+        check(qrk_dense_gemv_t(m_handle, top, m1, m1, m2, (const int32_t*)0, w1.ptr(), -1.0, du.ptr() + m1, t2.ptr(), m_lmWork.ptr()));
+        check(qrk_dense_solve_rt(m_handle, G, ldg, (int32_t)m2, t2.ptr()));
+        check(qrk_synchronize(m_handle));
+        double left[2];
+        Vector w2((size_t)m2);
+        check(qrk_memcpy(m_handle, left, s2.p, 2 * D, 1));
+        check(qrk_memcpy(m_handle, w2.data(), t2.p, m2 * D, 1));
+        double right = 0.0;
+        for (size_t k = 0; k < w2.size(); ++k) right += w2[k] * w2[k];
+        sums[1] = left[0] + right;
+        sums[2] = left[1];
         return x;
     }
+
+  public:
 
     Index rows() const { return m_rows; }
     Index cols() const { return m_cols; }
@@ -1995,6 +2109,7 @@ class BlockAngularSparseQR {
     bool m_qless = false;               // the last factorisation was factorizeAndSolve()
     bool m_lmReady = false;             // ... and took the fused route: W holds the factors lmSolve() works on
     Scratch m_lmTop, m_lmG, m_lmS, m_lmIdx;   // device: top panel, right stack, damped left factors, column indices of lmSolve(), kept between calls
+    Scratch m_lmWork;                   // device: the workspace of qrk_dense_gemv_t (lmpar() / lmGradient())
     DenseDeviceQR m_lmDense;            // the un-pivoted factorisation of the right stack
     std::vector<double> m_hc;
     std::vector<int> m_P2;

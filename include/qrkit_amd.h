@@ -371,6 +371,65 @@ const char* qrk_bd_lm_panel_kernel_name(qrk_bd_plan plan, int64_t ncols);
 qrk_status qrk_dense_lm_stack(qrk_handle h, const double* qr, int64_t lda, int32_t m2, const double* y2,
                               const double* diag2, const int32_t* perm2, double par, int64_t m1, double* g, int64_t ldg);
 
+/* ------------------------------------ block-angular: lmpar on the kept factors */
+
+/* In the pivoted order the damped triangular factor of [J1 | J2] is S^ = [S1 Top; 0 Rg]: S1 = the tiles qrk_bd_lm_panel writes to
+ * s_vals, Top = top(:, 0:m2), Rg = the upper triangle of the factorised right stack G(0:m2, 0:m2).  One evaluation of lmpar needs
+ * s1 = || S^-T u ||^2 with u = D~^2 z (z = the solution in pivoted order), by forward substitution:
+ *     w1 = S1^-T u1 (qrk_bd_solve_rt),  w2 = Rg^-T (u2 - Top^T w1) (qrk_dense_gemv_t, qrk_dense_solve_rt),  s1 = |w1|^2 + |w2|^2
+ * and once per lmpar the gradient of the undamped factors, g1 = R1^T y1 (qrk_bd_lm_gradient), g2 = Strip(:, P2)^T y1 + R2^T y2
+ * (qrk_dense_gemv_t, qrk_dense_trmv_t).  The four calls are DEVICE-pointer, enqueue-only calls on the handle's stream. */
+
+/* Per tile t: w_t = R_t^-T u_t, r_vals in the packed layout of qrk_bd_solve_r (s_vals of qrk_bd_lm_panel is passed here).
+ *   u, w [mat_cols]  : tile t's entries at its base_col; distinct arrays
+ *   sums2 [2]        : may be NULL.  sums2[0] = || w ||^2, sums2[1] = the number of tiles with an exact zero on the diagonal; such a
+ *                      tile gets w_t = 0 and adds nothing to sums2[0]
+ * Plan support is that of qrk_bd_lm_solve (QRK_STATUS_UNSUPPORTED otherwise); a NULL plan, r_vals, u or w is
+ * QRK_STATUS_INVALID_ARGUMENT before a device is touched.  The sums follow the rule of the qrk_bd_lm_* calls: one partial per workgroup
+ * in the plan's LM scratch, one workgroup adds them in a fixed order, no floating-point atomics, the grid depends on the plan alone:
+ * two identical calls give identical bits.  If sums2 is given, the scratch does not exist yet and the stream is being captured, the
+ * call fails with QRK_STATUS_INVALID_ARGUMENT instead of allocating (as qrk_bd_lmpar_device). */
+qrk_status qrk_bd_solve_rt(qrk_bd_plan plan, const double* r_vals, const double* u, double* w, double* sums2);
+
+/* Name of the kernel qrk_bd_solve_rt runs on this plan, or a string that contains "unsupported" where it would refuse ("" for a
+ * NULL plan).  The pointer is static. */
+const char* qrk_bd_solve_rt_kernel_name(qrk_bd_plan plan);
+
+/* out[j] = alpha sum_{i < rows} A(i, colidx[j]) w[i] + (add ? add[j] : 0) for j < cols: a tall-skinny A^T w read once.  A is
+ * column-major with leading dimension lda >= rows; rows rows .. lda of a column are never read; colidx NULL = column j.  alpha is
+ * +1 or -1.  rows = 0 gives out = add (0 when add is NULL); cols = 0 writes nothing.  out, add and w are distinct.
+ *   work : qrk_dense_gemv_t_work(rows, cols) doubles of the caller's (the call allocates nothing and can be captured): one partial
+ *          per chunk of rows and column; a second kernel adds the chunks of a column in a fixed order.
+ * No atomics; the grid and the order depend on (rows, cols) alone: two identical calls give identical bits. */
+int64_t    qrk_dense_gemv_t_work(int64_t rows, int64_t cols);
+qrk_status qrk_dense_gemv_t(qrk_handle h, const double* A, int64_t lda, int64_t rows, int64_t cols, const int32_t* colidx,
+                            const double* w, double alpha, const double* add, double* out, double* work);
+
+/* b(0:n) <- R^-T b(0:n), R = the upper triangle of qr (column-major, leading dimension lda >= n): nothing below the diagonal is
+ * read (a packed QR keeps reflectors there).  A zero on the diagonal gives non-finite entries.  n = 0 writes nothing. */
+qrk_status qrk_dense_solve_rt(qrk_handle h, const double* qr, int64_t lda, int32_t n, double* b);
+/* out[j] += sum_{i <= j} R(i, j) y[i] for j < n (out and y distinct), R as above. */
+qrk_status qrk_dense_trmv_t(qrk_handle h, const double* qr, int64_t lda, int32_t n, const double* y, double* out);
+
+/* The scalar rule of lmpar -- steps 1-5 of qrk_bd_lmpar above with every stopping rule, the parl / paru bounds, the DBL_MIN cases
+ * and the cap of 10 passes, the same correctly rounded operations in the same order -- as a host state machine for a caller that
+ * owns the evaluation (the block-angular facades).  No device is touched.
+ *   qrk_lmpar_begin : behind the evaluation at par = 0 (s0 = || D x ||^2, s1 = || S^-T D^2 z ||^2, s2 > 0 = a zero on R's
+ *                     diagonal, gnorm2 = | D^-1 g |^2).  delta > 0, par0 >= 0.
+ *   qrk_lmpar_next  : behind the evaluation at state->par.
+ * Both return 1 = evaluate at state->par and call qrk_lmpar_next, 0 = stop: state->par is the result, or -1 for a NULL state,
+ * delta <= 0, par0 < 0 or NaN, or a call after the stop.  state->iters = the passes of the loop so far, state->trace = (par, s0, s1)
+ * of every evaluation, the one at par = 0 first, the rows of evaluations that did not run zero. */
+typedef struct qrk_lmpar_state {
+    double par;            /* the par to evaluate next; the result after the stop */
+    double delta, parl, paru, fp, gnorm;
+    int32_t iters;
+    int32_t done;
+    double trace[33];
+} qrk_lmpar_state;
+int qrk_lmpar_begin(qrk_lmpar_state* state, double delta, double par0, double s0, double s1, double s2, double gnorm2);
+int qrk_lmpar_next(qrk_lmpar_state* state, double s0, double s1);
+
 /* --------------------------------------------- dense right-block solver (angular) */
 
 /* A single dense Householder QR with implicit Q: the _BlockQRSolverRight of

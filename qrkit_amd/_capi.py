@@ -35,7 +35,15 @@ EXPORTS = (
     "qrk_bd_factorize_apply_qt", "qrk_bd_panel_kernel_name",
     "qrk_bd_lm_solve", "qrk_bd_lm_gradient", "qrk_bd_r_col_norms", "qrk_bd_lmpar", "qrk_bd_lmpar_device", "qrk_bd_lm_kernel_name",
     "qrk_bd_lm_panel", "qrk_bd_lm_panel_kernel_name", "qrk_dense_lm_stack",
+    "qrk_bd_solve_rt", "qrk_bd_solve_rt_kernel_name", "qrk_dense_gemv_t_work", "qrk_dense_gemv_t", "qrk_dense_solve_rt",
+    "qrk_dense_trmv_t", "qrk_lmpar_begin", "qrk_lmpar_next",
 )
+
+
+class LmparState(C.Structure):
+    """qrk_lmpar_state of include/qrkit_amd.h."""
+    _fields_ = [("par", C.c_double), ("delta", C.c_double), ("parl", C.c_double), ("paru", C.c_double), ("fp", C.c_double),
+                ("gnorm", C.c_double), ("iters", C.c_int32), ("done", C.c_int32), ("trace", C.c_double * 33)]
 
 
 class Shard(C.Structure):
@@ -131,6 +139,22 @@ def lib() -> C.CDLL:
     L.qrk_bd_lm_panel_kernel_name.argtypes = [vp, C.c_int64]
     L.qrk_dense_lm_stack.restype = C.c_int
     L.qrk_dense_lm_stack.argtypes = [vp, dp, C.c_int64, C.c_int32, dp, dp, ip, C.c_double, C.c_int64, dp, C.c_int64]
+    L.qrk_bd_solve_rt.restype = C.c_int
+    L.qrk_bd_solve_rt.argtypes = [vp, dp, dp, dp, dp]
+    L.qrk_bd_solve_rt_kernel_name.restype = C.c_char_p
+    L.qrk_bd_solve_rt_kernel_name.argtypes = [vp]
+    L.qrk_dense_gemv_t_work.restype = C.c_int64
+    L.qrk_dense_gemv_t_work.argtypes = [C.c_int64, C.c_int64]
+    L.qrk_dense_gemv_t.restype = C.c_int
+    L.qrk_dense_gemv_t.argtypes = [vp, dp, C.c_int64, C.c_int64, C.c_int64, ip, dp, C.c_double, dp, dp, dp]
+    L.qrk_dense_solve_rt.restype = C.c_int
+    L.qrk_dense_solve_rt.argtypes = [vp, dp, C.c_int64, C.c_int32, dp]
+    L.qrk_dense_trmv_t.restype = C.c_int
+    L.qrk_dense_trmv_t.argtypes = [vp, dp, C.c_int64, C.c_int32, dp, dp]
+    L.qrk_lmpar_begin.restype = C.c_int
+    L.qrk_lmpar_begin.argtypes = [C.POINTER(LmparState), C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]
+    L.qrk_lmpar_next.restype = C.c_int
+    L.qrk_lmpar_next.argtypes = [C.POINTER(LmparState), C.c_double, C.c_double]
     L.qrk_dense_plan_create.restype = C.c_int
     L.qrk_dense_plan_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int, C.POINTER(vp)]
     L.qrk_dense_plan_destroy.restype = C.c_int

@@ -535,20 +535,36 @@ class BlockAngularSparseQR:
         || D x ||^2 (a float, from the returned x).  The dense factorisation of G synchronises the stream when
         (m1 + 2 m2) * m2 >= 2^18 (qrk_dense_factorize): the call cannot be captured into a graph at those sizes.
         Raises before a factorizeAndSolve() / computeAndSolve() that took the fused route (rows - m1 >= m2)."""
-        if not (self.m_isInitialized and self._qless and self._lm_ready):
-            raise RuntimeError("lmSolve(): no kept factors; call factorizeAndSolve() or computeAndSolve() first "
-                               "(with rows - m1 >= m2: the explicit route keeps none)")
+        self._lm_require("lmSolve()")
         par = float(par)
         if not par >= 0.0:
             raise ValueError("lmSolve(): par must be >= 0")
+        d = self._lm_diag(diag)
+        x, _ = self._lm_evaluate(d, par, False)
+        dx2 = None
+        if returnDxNorm2:
+            dx2 = float(torch.sum((x * d) ** 2 if d is not None else x ** 2).item())
+        xo = x.cpu().numpy() if self._lm_np else x
+        return (xo, dx2) if returnDxNorm2 else xo
+
+    def _lm_require(self, who: str):
+        if not (self.m_isInitialized and self._qless and self._lm_ready):
+            raise RuntimeError(f"{who}: no kept factors; call factorizeAndSolve() or computeAndSolve() first "
+                               "(with rows - m1 >= m2: the explicit route keeps none)")
+
+    def _lm_diag(self, diag):
+        """diag as cols() float64 entries on the device (None stays None)."""
+        if diag is None:
+            return None
+        d = (torch.as_tensor(np.asarray(diag, dtype=np.float64)) if not isinstance(diag, torch.Tensor) else diag)
+        d = d.reshape(-1).to(self._ctx.device, torch.float64).contiguous()
+        assert d.numel() == self._m1 + self._m2, "diag: expected cols() entries"
+        return d
+
+    def _lm_arrays(self):
+        """The work arrays and the dense plan of the damped evaluation, kept between calls of one shape."""
         dev = self._ctx.device
-        m1, m2, rows, W = self._m1, self._m2, self._rows, self._W
-        left = self.m_leftSolver
-        d = None
-        if diag is not None:
-            d = (torch.as_tensor(np.asarray(diag, dtype=np.float64)) if not isinstance(diag, torch.Tensor) else diag)
-            d = d.reshape(-1).to(dev, torch.float64).contiguous()
-            assert d.numel() == m1 + m2, "diag: expected cols() entries"
+        m1, m2, left = self._m1, self._m2, self.m_leftSolver
         ldg = m1 + 2 * m2
         lm = self._lm
         if lm is None or lm["key"] != (m1, m2, left._nnz_r):
@@ -560,6 +576,31 @@ class BlockAngularSparseQR:
                 "dense": DenseColPivQR(self._ctx, capi.HOUSEHOLDER),
                 "colidx": torch.empty(m2 + 1, dtype=torch.int32, device=dev),
             }
+        return lm
+
+    def _lm_transposed_arrays(self):
+        """What the transposed pass and the gradient add to _lm_arrays(): w1, the right vector, the sums and gemv_t's workspace."""
+        lm = self._lm_arrays()
+        if "w1" not in lm:
+            dev = self._ctx.device
+            m1, m2 = self._m1, self._m2
+            lm["w1"] = torch.empty(max(m1, 1), dtype=torch.float64, device=dev)
+            lm["t2"] = torch.empty(max(m2, 1), dtype=torch.float64, device=dev)
+            lm["sums2"] = torch.empty(2, dtype=torch.float64, device=dev)
+            lm["work"] = torch.empty(int(capi.lib().qrk_dense_gemv_t_work(m1, m2)), dtype=torch.float64, device=dev)
+        return lm
+
+    def _lm_evaluate(self, d, par: float, transposed: bool):
+        """One damped evaluation on the kept factors: lmSolve()'s chain, and with `transposed` the forward substitution with the
+        damped factor S^ = [S1 Top; 0 Rg] behind it: u = D~^2 z in pivoted order, w1 = S1^-T u1 (qrk_bd_solve_rt
+        on s_vals), w2 = Rg^-T (u2 - Top^T w1) (qrk_dense_gemv_t on top, qrk_dense_solve_rt on G's upper triangle).  d: the device
+        diag or None.  Returns (x, None), x on the device in J's column order, or (x, (s0, s1, zeros)) with s0 = || D x ||^2,
+        s1 = || S^-T u ||^2 and the number of S1's tiles with a zero on the diagonal, brought over in one read-back."""
+        dev = self._ctx.device
+        m1, m2, rows, W = self._m1, self._m2, self._rows, self._W
+        left = self.m_leftSolver
+        ldg = m1 + 2 * m2
+        lm = self._lm_transposed_arrays() if transposed else self._lm_arrays()
         top, G, s_vals, colidx = lm["top"], lm["G"], lm["s"], lm["colidx"]
         p2 = self.m_rightSolver.colsPermutation()
         colidx[:m2].copy_(p2)
@@ -579,12 +620,85 @@ class BlockAngularSparseQR:
         z1 = torch.empty_like(rhs1)
         capi.check(L.qrk_bd_solve_r(left._plan, s_vals.data_ptr(), rhs1.data_ptr(), 1, z1.data_ptr(), capi.MEM_DEVICE), h)
         x = torch.empty(m1 + m2, dtype=torch.float64, device=dev)
-        x[self.m_outputPerm_c.long()] = torch.cat([z1.reshape(-1), z2.reshape(-1)])
-        dx2 = None
-        if returnDxNorm2:
-            dx2 = float(torch.sum((x * d) ** 2 if d is not None else x ** 2).item())
+        pc = self.m_outputPerm_c.long()
+        zz = torch.cat([z1.reshape(-1), z2.reshape(-1)])
+        x[pc] = zz
+        if not transposed:
+            return x, None
+        u = zz * d[pc] ** 2 if d is not None else zz                 # (contiguous: u1 = its first m1 entries, u2 the rest)
+        w1, t2, sums2, work = lm["w1"], lm["t2"], lm["sums2"], lm["work"]
+        capi.check(L.qrk_bd_solve_rt(left._plan, s_vals.data_ptr(), u.data_ptr(), w1.data_ptr(), sums2.data_ptr()), h)
+        capi.check(L.qrk_dense_gemv_t(h, top.data_ptr(), max(m1, 1), m1, m2, None, w1.data_ptr(), -1.0, u.data_ptr() + 8 * m1,
+                                      t2.data_ptr(), work.data_ptr()), h)
+        capi.check(L.qrk_dense_solve_rt(h, G.data_ptr(), ldg, m2, t2.data_ptr()), h)
+        s0 = torch.sum((x * d) ** 2 if d is not None else x ** 2)
+        s = torch.cat([s0.reshape(1), sums2, torch.sum(t2[:m2] ** 2).reshape(1)]).cpu().numpy()     # the one read-back
+        return x, (float(s[0]), float(s[1]) + float(s[3]), float(s[2]))
+
+    def lmGradient(self, diag=None):
+        """(g, gnorm): g = J^T b in J's column order and gnorm = || D^-1 g ||, from the UNDAMPED kept factors (what lmpar's upper
+        bound needs): g = P R^^T y with R^ = [R1 Strip(:, P2); 0 R2] and y = Q^T b, so g1 = R1^T y1 (qrk_bd_lm_gradient on the left
+        plan) and g2 = Strip(:, P2)^T y1 + R2^T y2 (qrk_dense_gemv_t on W's strip, qrk_dense_trmv_t on R2).  diag as for lmSolve().
+        g is numpy or a tensor as `b` was given to factorizeAndSolve(); gnorm is a float."""
+        self._lm_require("lmGradient()")
+        g, gnorm2 = self._lm_gradient(self._lm_diag(diag))
+        return (g.cpu().numpy() if self._lm_np else g), float(np.sqrt(gnorm2))
+
+    def _lm_gradient(self, d):
+        dev = self._ctx.device
+        m1, m2, rows, W = self._m1, self._m2, self._rows, self._W
+        left = self.m_leftSolver
+        lm = self._lm_transposed_arrays()
+        L, h = capi.lib(), self._ctx.handle
+        self._ctx.use_current_stream()
+        y1 = W.data_ptr() + 8 * m2 * rows                   # y = Q^T b = W(:, m2); R2 = the upper triangle of W(m1:, 0:m2)
+        g = torch.empty(m1 + m2, dtype=torch.float64, device=dev)
+        g2 = torch.empty(max(m2, 1), dtype=torch.float64, device=dev)
+        n2 = torch.empty(1, dtype=torch.float64, device=dev)
+        capi.check(L.qrk_bd_lm_gradient(left._plan, left._r.data_ptr(), left._perm.data_ptr(), y1, d.data_ptr() if d is not None else None,
+                                        g.data_ptr(), n2.data_ptr(), capi.MEM_DEVICE), h)
+        p2 = self.m_rightSolver.colsPermutation()
+        capi.check(L.qrk_dense_gemv_t(h, W.data_ptr(), rows, m1, m2, p2.data_ptr(), y1, 1.0, None, g2.data_ptr(), lm["work"].data_ptr()), h)
+        capi.check(L.qrk_dense_trmv_t(h, W.data_ptr() + 8 * m1, rows, m2, y1 + 8 * m1, g2.data_ptr()), h)
+        g[m1 + self._P2] = g2[:m2]
+        q2 = g[m1:] / d[m1:] if d is not None else g[m1:]
+        gnorm2 = float((n2[0] + torch.sum(q2 ** 2)).item())
+        return g, gnorm2
+
+    def lmpar(self, diag, delta: float, par: float = 0.0, returnTrace: bool = False):
+        """MINPACK's lmpar on the kept factors (what Eigen::LevenbergMarquardt calls between two factorisations,
+        examples/ellipse_fitting.cpp:257-280): finds par with | || D x || - delta | <= 0.1 delta, or par = 0 when the Gauss-Newton
+        step is inside the region.  A host loop: every evaluation is lmSolve()'s chain and the transposed pass behind it
+        (_lm_evaluate) with one read-back of the sums, the scalar rule is qrk_lmpar_begin / qrk_lmpar_next (steps 1-5 of
+        qrk_bd_lmpar, include/qrkit_amd.h), the gradient of the upper bound is lmGradient()'s.  At most 11 evaluations.
+
+        diag as for lmSolve(); delta > 0; par >= 0 is the start value.  Returns (x, par, iters), x as lmSolve(diag, par) returns
+        it -- the same bits --, and with returnTrace also the (iters + 1) x 3 array of (par, || D x ||^2, || S^-T D^2 z ||^2) per
+        evaluation.  Rank-deficient undamped factors are not handled: a zero on the diagonal at par = 0 raises."""
+        self._lm_require("lmpar()")
+        delta, par = float(delta), float(par)
+        if not delta > 0.0:
+            raise ValueError("lmpar(): delta must be > 0")
+        if not par >= 0.0:
+            raise ValueError("lmpar(): par must be >= 0")
+        d = self._lm_diag(diag)
+        L = capi.lib()
+        x, (s0, s1, zeros) = self._lm_evaluate(d, 0.0, True)
+        if zeros > 0 or not np.isfinite(s1):
+            raise RuntimeError("lmpar(): the undamped factors have a zero on the diagonal (rank-deficient J is not supported)")
+        _, gnorm2 = self._lm_gradient(d)
+        st = capi.LmparState()
+        rc = L.qrk_lmpar_begin(C.byref(st), delta, par, s0, s1, 0.0, gnorm2)
+        while rc == 1:
+            x, (s0, s1, _) = self._lm_evaluate(d, st.par, True)
+            rc = L.qrk_lmpar_next(C.byref(st), s0, s1)
+        if rc != 0:
+            raise RuntimeError("lmpar(): the scalar rule refused its arguments")
         xo = x.cpu().numpy() if self._lm_np else x
-        return (xo, dx2) if returnDxNorm2 else xo
+        out = (xo, float(st.par), int(st.iters))
+        if returnTrace:
+            out += (np.array(st.trace[:3 * (st.iters + 1)], dtype=np.float64).reshape(-1, 3),)
+        return out
 
     def _need_q(self, what: str):
         if self._qless:

@@ -1560,6 +1560,120 @@ qrk_status qrk_dense_lm_stack(qrk_handle h, const double* qr, int64_t lda, int32
     return QRK_STATUS_OK;
 }
 
+// ---- the transposed pass of lmpar on the block-angular factors (angular_lmpar.hip)
+qrk_status qrk_bd_solve_rt(qrk_bd_plan p, const double* r_vals, const double* u, double* w, double* sums2)
+{
+    if (!p || !r_vals || !u || !w)
+        return fail(p ? p->h : nullptr, QRK_STATUS_INVALID_ARGUMENT, "qrk_bd_solve_rt: bad argument (NULL plan or buffer)");
+    qrk_handle h = p->h;
+    if (const char* why = lm_unsupported(p)) return fail(h, QRK_STATUS_UNSUPPORTED, std::string("qrk_bd_solve_rt: ") + why);
+    QRK_HIP(h, hipSetDevice(h->device));
+    if (sums2 && !p->d_lm_scratch) {
+        // the one allocation of the LM calls; never under a stream capture (hipMalloc would invalidate it)
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        QRK_HIP(h, hipStreamIsCapturing(h->stream, &cs));
+        if (cs != hipStreamCaptureStatusNone)
+            return fail(h, QRK_STATUS_INVALID_ARGUMENT, "qrk_bd_solve_rt: the plan's scratch is not allocated yet and the stream is being "
+                                                        "captured: call it once outside the capture first");
+        if (qrk_status st = ensure_lm_scratch(p, "qrk_bd_solve_rt")) return st;
+    }
+    QRK_HIP(h, qrk::launch_bd_solve_rt(make_geom(p), p->max_cols, r_vals, u, w, p->d_lm_scratch, sums2, h->stream));
+    return QRK_STATUS_OK;
+}
+
+const char* qrk_bd_solve_rt_kernel_name(qrk_bd_plan p)
+{
+    if (!p) return "";
+    if (p->q_format != QRK_FULL_Q) return "unsupported: R is upper triangular only in the FullQ format";
+    const int G = qrk::bd_solve_rt_group_width(p->max_cols);
+    if (G < 0) return "unsupported: a tile of this plan has more than 32 columns";
+    return G == 0 ? "qrk::lm::bd_solve_rt_thin_kernel" : "qrk::lm::bd_solve_rt_group_kernel";
+}
+
+int64_t qrk_dense_gemv_t_work(int64_t rows, int64_t cols) { return qrk::dense_gemv_t_work(rows, cols); }
+
+qrk_status qrk_dense_gemv_t(qrk_handle h, const double* A, int64_t lda, int64_t rows, int64_t cols, const int32_t* colidx,
+                            const double* w, double alpha, const double* add, double* out, double* work)
+{
+    if (!h || rows < 0 || cols < 0 || lda < rows || !(alpha == 1.0 || alpha == -1.0) || (cols > 0 && (!out || !work)) ||
+        (rows > 0 && cols > 0 && (!A || !w)))
+        return fail(h, QRK_STATUS_INVALID_ARGUMENT, "qrk_dense_gemv_t: bad argument (NULL handle or buffer, negative size, lda < rows, or alpha not +-1)");
+    if (cols == 0) return QRK_STATUS_OK;
+    QRK_HIP(h, hipSetDevice(h->device));
+    QRK_HIP(h, qrk::launch_dense_gemv_t(A, lda, rows, cols, colidx, w, alpha, add, out, work, h->stream));
+    return QRK_STATUS_OK;
+}
+
+qrk_status qrk_dense_solve_rt(qrk_handle h, const double* qr, int64_t lda, int32_t n, double* b)
+{
+    if (!h || n < 0 || (n > 0 && (!qr || !b || lda < n)))
+        return fail(h, QRK_STATUS_INVALID_ARGUMENT, "qrk_dense_solve_rt: bad argument");
+    if (n == 0) return QRK_STATUS_OK;
+    QRK_HIP(h, hipSetDevice(h->device));
+    QRK_HIP(h, qrk::launch_dense_solve_rt(qr, lda, n, b, h->stream));
+    return QRK_STATUS_OK;
+}
+
+qrk_status qrk_dense_trmv_t(qrk_handle h, const double* qr, int64_t lda, int32_t n, const double* y, double* out)
+{
+    if (!h || n < 0 || (n > 0 && (!qr || !y || !out || lda < n)))
+        return fail(h, QRK_STATUS_INVALID_ARGUMENT, "qrk_dense_trmv_t: bad argument");
+    if (n == 0) return QRK_STATUS_OK;
+    QRK_HIP(h, hipSetDevice(h->device));
+    QRK_HIP(h, qrk::launch_dense_trmv_t(qr, lda, n, y, out, h->stream));
+    return QRK_STATUS_OK;
+}
+
+// The scalar rule of lmpar as a host state machine: qrk_bd_lmpar's steps 1-5, operation for operation (no a * b + c in it, and the
+// pragma keeps it so)
+int qrk_lmpar_begin(qrk_lmpar_state* st, double delta, double par0, double s0, double s1, double s2, double gnorm2)
+{
+#pragma clang fp contract(off)
+    if (!st || !(delta > 0.0) || !(par0 >= 0.0)) return -1;
+    std::memset(st, 0, sizeof(*st));
+    st->trace[0] = 0.0; st->trace[1] = s0; st->trace[2] = s1;
+    st->delta = delta;
+    st->done = 1;
+    const double dxnorm = std::sqrt(s0);
+    const double fp = dxnorm - delta;
+    st->fp = fp;
+    if (fp <= 0.1 * delta) { st->par = 0.0; return 0; }
+    const double parl = (s2 > 0.0 || !(s1 > 0.0)) ? 0.0 : fp / (delta * s1 / s0);
+    const double gnorm = std::sqrt(gnorm2);
+    double paru = gnorm / delta;
+    if (paru == 0.0) paru = DBL_MIN / std::min(delta, 0.1);
+    double pv = std::min(std::max(par0, parl), paru);
+    if (pv == 0.0) pv = gnorm / dxnorm;
+    if (pv == 0.0) pv = std::max(DBL_MIN, 0.001 * paru);          // (the head of pass 1)
+    st->par = pv; st->parl = parl; st->paru = paru; st->gnorm = gnorm;
+    st->done = 0;
+    return 1;
+}
+
+int qrk_lmpar_next(qrk_lmpar_state* st, double s0, double s1)
+{
+#pragma clang fp contract(off)
+    if (!st || st->done || st->iters < 0 || st->iters >= 10) return -1;
+    const int iter = ++st->iters;
+    double pv = st->par, parl = st->parl, paru = st->paru;
+    const double delta = st->delta, temp = st->fp;
+    st->trace[3 * iter] = pv; st->trace[3 * iter + 1] = s0; st->trace[3 * iter + 2] = s1;
+    const double dxnorm = std::sqrt(s0);
+    const double fp = dxnorm - delta;
+    st->fp = fp;
+    if (std::fabs(fp) <= 0.1 * delta || (parl == 0.0 && fp <= temp && temp < 0.0) || iter == 10) {
+        st->done = 1;
+        return 0;
+    }
+    const double parc = fp / (delta * s1 / s0);
+    if (fp > 0.0) parl = std::max(parl, pv);
+    if (fp < 0.0) paru = std::min(paru, pv);
+    pv = std::max(parl, pv + parc);
+    if (pv == 0.0) pv = std::max(DBL_MIN, 0.001 * paru);          // (the head of the next pass)
+    st->par = pv; st->parl = parl; st->paru = paru;
+    return 1;
+}
+
 qrk_status qrk_dense_plan_create(qrk_handle h, int32_t rows, int32_t cols, qrk_block_solver solver,
                                  qrk_dense_plan* out)
 {

@@ -286,6 +286,17 @@ hipError_t launch_bd_lm_panel(const TileGeom& g, int max_cols, const double* r_v
 hipError_t launch_dense_lm_stack(const double* qr, int64_t lda, int m2, const double* y2, const double* diag2, const int32_t* perm2,
                                  double par, int64_t m1, double* gs, int64_t ldg, hipStream_t stream);
 
+// angular_lmpar.hip: the transposed pass of lmpar on the block-angular factors
+int bd_solve_rt_group_width(int max_cols);      // 0: one lane per tile; 4 .. 32 lanes per tile; -1: not supported
+// w_t = R_t^-T u_t per tile; partials: 2 * BD_LM_MAX_BLOCKS doubles of scratch, only used when sums2 (2 doubles) is given
+hipError_t launch_bd_solve_rt(const TileGeom& g, int max_cols, const double* r_vals, const double* u, double* w, double* partials,
+                              double* sums2, hipStream_t stream);
+int64_t dense_gemv_t_work(int64_t rows, int64_t cols);
+hipError_t launch_dense_gemv_t(const double* A, int64_t lda, int64_t rows, int64_t cols, const int32_t* colidx, const double* w,
+                               double alpha, const double* add, double* out, double* work, hipStream_t stream);
+hipError_t launch_dense_solve_rt(const double* qr, int64_t lda, int n, double* b, hipStream_t stream);
+hipError_t launch_dense_trmv_t(const double* qr, int64_t lda, int n, const double* y, double* out, hipStream_t stream);
+
 // ---- decision margins of the fast kernels ------------------------------------------------
 // A fast kernel (FMA chains, squared column norms, un-normalised reflector) takes a data-dependent decision of the reference
 // algorithm only when it is clear of rounding, and otherwise sends the tile to the exact path (bdqr_exact.hip), which repeats
