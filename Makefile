@@ -43,6 +43,8 @@ cpptest: $(LIB)
 	    -Wl,-rpath,'$$ORIGIN/../qrkit_amd/lib' -o build/test_angular_lm
 	g++ -O2 -std=c++14 -Wall -Iinclude tests/cpp/test_angular_lmpar.cpp -Lqrkit_amd/lib -lqrkit_amd \
 	    -Wl,-rpath,'$$ORIGIN/../qrkit_amd/lib' -o build/test_angular_lmpar
+	g++ -O2 -std=c++14 -Wall -Iinclude tests/cpp/test_angular_lm_reduced.cpp -Lqrkit_amd/lib -lqrkit_amd \
+	    -Wl,-rpath,'$$ORIGIN/../qrkit_amd/lib' -o build/test_angular_lm_reduced
 	g++ -O2 -std=c++14 -Wall -D__HIP_PLATFORM_AMD__ -Iinclude -I/opt/rocm/include tests/cpp/test_sharded.cpp -Lqrkit_amd/lib -lqrkit_amd \
 	    -L/opt/rocm/lib -lrccl -lamdhip64 -Wl,-rpath,'$$ORIGIN/../qrkit_amd/lib' -Wl,-rpath,/opt/rocm/lib -o build/test_sharded
 

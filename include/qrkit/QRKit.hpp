@@ -1393,6 +1393,71 @@ class BlockedThinDenseQR {
     PermutationType m_outputPerm_c, m_rowPerm;
 };
 // ---------------------------------------------------------------------------------------------
+// The R factor of a tall-skinny dense matrix without Q (qrk_dense_qless_r): R^T R = A^T A by a tree of Householder
+// factorisations whose reflectors are never stored; at most 32 columns, any number of rows (missing rows count as zero),
+// deterministic.  compute() takes a host matrix (it crosses PCIe once), computeDevice() a column-major device array with leading
+// dimension lda >= rows, which is only read.  The device buffers are kept between calls of one shape.
+class DenseQlessR {
+  public:
+    explicit DenseQlessR(int device = 0) : m_handle(0), m_dA(0), m_dR(0), m_dWork(0), m_capA(0), m_capWork(0), m_rows(0), m_cols(0) {
+        if (qrk_create(&m_handle, device, 0) != QRK_STATUS_OK)
+            throw std::runtime_error(std::string("qrkit: ") + qrk_last_error(0));
+    }
+    ~DenseQlessR() {
+        if (m_dA) qrk_device_free(m_handle, m_dA);
+        if (m_dR) qrk_device_free(m_handle, m_dR);
+        if (m_dWork) qrk_device_free(m_handle, m_dWork);
+        if (m_handle) qrk_destroy(m_handle);
+    }
+    DenseQlessR(const DenseQlessR&) = delete;
+    DenseQlessR& operator=(const DenseQlessR&) = delete;
+
+    DenseQlessR& compute(const Matrix& mat) {
+        const int64_t bytes = std::max<int64_t>(mat.rows() * mat.cols(), 1) * (int64_t)sizeof(double);
+        if (bytes > m_capA) {
+            if (m_dA) { qrk_device_free(m_handle, m_dA); m_dA = 0; m_capA = 0; }
+            check(qrk_device_alloc(m_handle, bytes, &m_dA));
+            m_capA = bytes;
+        }
+        if (mat.rows() * mat.cols() > 0) check(qrk_memcpy(m_handle, m_dA, mat.data(), mat.rows() * mat.cols() * (int64_t)sizeof(double), 0));
+        return computeDevice((const double*)m_dA, mat.rows(), mat.rows(), mat.cols());
+    }
+    DenseQlessR& computeDevice(const double* dA, Index lda, Index rows, Index cols) {
+        if (cols > 32) throw std::invalid_argument("qrkit: DenseQlessR: more than 32 columns");
+        const int64_t D = (int64_t)sizeof(double), work = qrk_dense_qless_r_work(rows, (int32_t)cols) * D;
+        if (work > m_capWork) {
+            if (m_dWork) { qrk_device_free(m_handle, m_dWork); m_dWork = 0; m_capWork = 0; }
+            check(qrk_device_alloc(m_handle, work, &m_dWork));
+            m_capWork = work;
+        }
+        if (cols != m_cols || !m_dR) {
+            if (m_dR) { qrk_device_free(m_handle, m_dR); m_dR = 0; }
+            check(qrk_device_alloc(m_handle, std::max<int64_t>(cols * cols, 1) * D, &m_dR));
+        }
+        m_rows = rows; m_cols = cols;
+        check(qrk_dense_qless_r(m_handle, dA, lda, rows, (int32_t)cols, (double*)m_dR, std::max<Index>(cols, 1), (double*)m_dWork));
+        check(qrk_synchronize(m_handle));
+        m_R = Matrix(cols, cols);
+        if (cols > 0) check(qrk_memcpy(m_handle, m_R.data(), m_dR, cols * cols * D, 1));
+        return *this;
+    }
+    Index rows() const { return m_rows; }
+    Index cols() const { return m_cols; }
+    // cols x cols, upper triangular with exact zeros below the diagonal; the sign of the diagonal is not specified
+    const Matrix& matrixR() const { return m_R; }
+    const double* matrixRDevice() const { return (const double*)m_dR; }
+
+  private:
+    void check(qrk_status st) const {
+        if (st != QRK_STATUS_OK) throw std::runtime_error(std::string("qrkit: ") + qrk_last_error(m_handle));
+    }
+    qrk_handle m_handle;
+    void *m_dA, *m_dR, *m_dWork;
+    int64_t m_capA, m_capWork;
+    Index m_rows, m_cols;
+    Matrix m_R;
+};
+// ---------------------------------------------------------------------------------------------
 // QRKit::BlockedThinSparseQR<MatrixType, SuggestedBlockCols> (BlockedThinSparseQR.h:105-283): column-pivoted QR of a thin SPARSE
 // matrix, panel by panel, with the ColumnDensity column ordering and the as-banded-as-possible row ordering (analyzePattern,
 // :168-201), per-panel ColPivHouseholderQR and the nonzero / zero pivot column bookkeeping (:250-256).  compute() hands the CSC
@@ -1565,6 +1630,10 @@ class BlockAngularSparseQR {
     ~BlockAngularSparseQR() {
         m_dense.release();
         m_lmDense.release();
+        m_lmDense2.release();
+        if (m_lmG2.p) qrk_device_free(m_handle, m_lmG2.p);
+        if (m_lmF.p) qrk_device_free(m_handle, m_lmF.p);
+        if (m_lmQWork.p) qrk_device_free(m_handle, m_lmQWork.p);
         if (m_lmTop.p) qrk_device_free(m_handle, m_lmTop.p);
         if (m_lmG.p) qrk_device_free(m_handle, m_lmG.p);
         if (m_lmS.p) qrk_device_free(m_handle, m_lmS.p);
@@ -1726,8 +1795,11 @@ class BlockAngularSparseQR {
     // qrk_bd_lm_panel triangularises [R1; sqrt(par) D1] tile by tile and takes the reflectors over W(0:m1, [P2, m2]); the fill lands
     // in the right stack G = [R2 y2; fill; sqrt(par) D2(P2) 0] (qrk_dense_lm_stack writes the other rows), G(:, 0:m2) is factorised
     // without pivoting, Q^T goes over its last column, and the back substitution is factorizeAndSolve()'s with the damped factors.
-    // The work arrays and the dense plan are kept between calls of one shape.  The dense factorisation of G synchronises the stream
-    // when (m1 + 2 m2) * m2 >= 2^18 (qrk_dense_factorize); this facade waits for every step in any case.
+    // The work arrays and the dense plan are kept between calls of one shape.  On the reduced route (lmRoute(); the default for
+    // m2 <= 31) the fill goes to a buffer of its own, qrk_dense_qless_r reduces it to one triangle T and the stack is
+    // G2 = [R2 y2; T; sqrt(par) D2(P2) 0], (3 m2 + 1) x (m2 + 1): the same minimiser, a factorisation that does not depend on m1.
+    // On the stacked route the dense factorisation of G synchronises the stream when (m1 + 2 m2) * m2 >= 2^18
+    // (qrk_dense_factorize); this facade waits for every step in any case.
     // Throws before a factorizeAndSolve() / computeAndSolve() that took the fused route (rows - m1 >= m2).
     Vector lmSolve(const Vector* diag, double par, double* dxnorm2 = 0) {
         lmRequire("lmSolve()", diag);
@@ -1799,6 +1871,24 @@ class BlockAngularSparseQR {
         return x;
     }
 
+    // How lmSolve() / lmpar() finish the right part: "stacked" factorises the (m1 + 2 m2) x m2 stack with the fill in it
+    // (K11: the same calls in the same order on the same arrays as before the routes existed), "reduced" first reduces
+    // [fill | its right-hand side] to one (m2 + 1) x (m2 + 1) triangle with qrk_dense_qless_r and factorises the (3 m2 + 1) x m2
+    // stack (needs m2 + 1 <= 32: throws at the next evaluation otherwise), "auto" (the default) takes the reduced route where it
+    // can.  Both give the same minimiser; each route repeats its own bits.
+    void setLmRoute(const std::string& route) {
+        if (route != "auto" && route != "reduced" && route != "stacked")
+            throw std::invalid_argument("qrkit: setLmRoute(): expected \"auto\", \"reduced\" or \"stacked\"");
+        m_lmRoute = route == "auto" ? std::string() : route;
+    }
+    // The route the next evaluation takes: "reduced" or "stacked".  Under "auto" it depends on m2, so it needs the kept factors.
+    std::string lmRoute() const {
+        if (!m_lmRoute.empty()) return m_lmRoute;
+        lmRequire("lmRoute()", 0);
+        return m_m2 >= 1 && m_m2 + 1 <= kLmReducedMaxCols ? "reduced" : "stacked";
+    }
+    enum { kLmReducedMaxCols = 32 };    // qrk_dense_qless_r's column limit
+
   private:
     void lmRequire(const char* who, const Vector* diag) const {
         if (!(m_isInitialized && m_qless && m_lmReady))
@@ -1810,10 +1900,17 @@ class BlockAngularSparseQR {
     // with u = D~^2 z and the number of S1's tiles with a zero on the diagonal.
     Vector lmEvaluate(const Vector* diag, double par, bool transposed, double* sums) {
         const int64_t D = (int64_t)sizeof(double);
-        const Index m1 = m_m1, m2 = m_m2, ldg = m1 + 2 * m2;
-        m_lmTop.reserve(*this, m1 * (m2 + 1)); m_lmG.reserve(*this, ldg * (m2 + 1));
+        const Index m1 = m_m1, m2 = m_m2;
+        const bool reduced = lmRoute() == "reduced";
+        if (reduced && !(m2 >= 1 && m2 + 1 <= kLmReducedMaxCols))
+            throw std::runtime_error("qrkit: the reduced LM route needs 1 <= m2 <= 31; setLmRoute(\"auto\") or \"stacked\"");
+        // the reduced stack G2 = [R2 y2; T; sqrt(par) D2(P2) 0] is (3 m2 + 1) x (m2 + 1); the big G exists only on the stacked route
+        const Index ldg = reduced ? 3 * m2 + 1 : m1 + 2 * m2;
+        Scratch& gbuf = reduced ? m_lmG2 : m_lmG;
+        DenseDeviceQR& dense = reduced ? m_lmDense2 : m_lmDense;
+        m_lmTop.reserve(*this, m1 * (m2 + 1)); gbuf.reserve(*this, ldg * (m2 + 1));
         m_lmS.reserve(*this, m_leftSolver.nonZerosR()); m_lmIdx.reserve(*this, (m2 + 2) / 2 + 1);
-        double *W = m_dW.ptr(), *top = m_lmTop.ptr(), *G = m_lmG.ptr(), *S = m_lmS.ptr();
+        double *W = m_dW.ptr(), *top = m_lmTop.ptr(), *G = gbuf.ptr(), *S = m_lmS.ptr();
         int32_t* colidx = (int32_t*)m_lmIdx.p;
         std::vector<int32_t> idx((size_t)(m2 + 1));
         for (Index j = 0; j < m2; ++j) idx[(size_t)j] = (int32_t)m_P2[(size_t)j];
@@ -1822,17 +1919,26 @@ class BlockAngularSparseQR {
         DBuf dd(*this, m_cols);
         if (diag) check(qrk_memcpy(m_handle, dd.p, diag->data(), m_cols * D, 0));
         const double* d1 = diag ? dd.ptr() : (const double*)0;
-        m_leftSolver.lmPanelDevice(d1, par, W, m_rows, m2 + 1, colidx, S, top, m1, G + m2, ldg);
+        if (reduced) {
+            // the fill to F, [F | f] to the triangle T in rows m2 .. 2 m2 + 1 of G2; the stack kernel sees a "fill" of m2 + 1 rows
+            const Index ldf = std::max<Index>(m1, 1);
+            m_lmF.reserve(*this, ldf * (m2 + 1));
+            m_lmQWork.reserve(*this, qrk_dense_qless_r_work(m1, (int32_t)(m2 + 1)));
+            m_leftSolver.lmPanelDevice(d1, par, W, m_rows, m2 + 1, colidx, S, top, m1, m_lmF.ptr(), ldf);
+            check(qrk_dense_qless_r(m_handle, m_lmF.ptr(), ldf, m1, (int32_t)(m2 + 1), G + m2, ldg, m_lmQWork.ptr()));
+        } else {
+            m_leftSolver.lmPanelDevice(d1, par, W, m_rows, m2 + 1, colidx, S, top, m1, G + m2, ldg);
+        }
         check(qrk_dense_lm_stack(m_handle, W + m1, m_rows, (int32_t)m2, W + m2 * m_rows + m1, diag ? dd.ptr() + m1 : (const double*)0,
-                                 m_dense.permDevice(), par, m1, G, ldg));
+                                 m_dense.permDevice(), par, reduced ? m2 + 1 : m1, G, ldg));
         std::vector<double> hc;
         std::vector<int32_t> pg;
-        m_lmDense.factorizeDeviceView(m_handle, G, ldg, ldg, m2, (int)QRK_HOUSEHOLDER, hc, pg);
-        m_lmDense.applyQDevice(G + m2 * ldg, 1, true);
+        dense.factorizeDeviceView(m_handle, G, ldg, ldg, m2, (int)QRK_HOUSEHOLDER, hc, pg);
+        dense.applyQDevice(G + m2 * ldg, 1, true);
         DBuf z2(*this, m2), y1(*this, m1), z1(*this, m1);
         check(qrk_memcpy_2d(m_handle, z2.p, m2 * D, G + m2 * ldg, m2 * D, m2 * D, 1, 2));
         check(qrk_memcpy_2d(m_handle, y1.p, m1 * D, top + m2 * m1, m1 * D, m1 * D, 1, 2));
-        m_lmDense.solveRDevice(z2.ptr(), m2, 1);
+        dense.solveRDevice(z2.ptr(), m2, 1);
         check(qrk_dense_gemv_sub(m_handle, top, m1, m1, m2, (const int32_t*)0, z2.ptr(), y1.ptr()));
         check(qrk_synchronize(m_handle));
         m_leftSolver.solveDampedDevice(S, y1.ptr(), 1, z1.ptr());
@@ -2111,6 +2217,9 @@ class BlockAngularSparseQR {
     Scratch m_lmTop, m_lmG, m_lmS, m_lmIdx;   // device: top panel, right stack, damped left factors, column indices of lmSolve(), kept between calls
     Scratch m_lmWork;                   // device: the workspace of qrk_dense_gemv_t (lmpar() / lmGradient())
     DenseDeviceQR m_lmDense;            // the un-pivoted factorisation of the right stack
+    Scratch m_lmG2, m_lmF, m_lmQWork;   // device, reduced route (K13): the small stack, the fill and the workspace of qrk_dense_qless_r
+    DenseDeviceQR m_lmDense2;           // ... and the factorisation of the small stack
+    std::string m_lmRoute;              // "auto" (empty), "reduced" or "stacked": setLmRoute()
     std::vector<double> m_hc;
     std::vector<int> m_P2;
     mutable MatrixRType m_R;            // host copy of R, assembled by the first matrixR()

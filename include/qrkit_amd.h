@@ -367,7 +367,10 @@ const char* qrk_bd_lm_panel_kernel_name(qrk_bd_plan plan, int64_t ncols);
  *                         reflectors below the diagonal are not copied, the rows below it are zero
  *   rows m2 + m1 ..     : sqrt(par) diag2[perm2[k]] on the diagonal (diag2 NULL = ones, perm2 NULL = identity), zero elsewhere, the
  *                         last column included
- * DEVICE pointers, enqueue-only on the handle's stream.  m2 = 0 writes nothing. */
+ * DEVICE pointers, enqueue-only on the handle's stream.  m2 = 0 writes nothing.
+ * The reduced route passes m1 = m2 + 1: qrk_bd_lm_panel writes its fill to a buffer of its own, qrk_dense_qless_r
+ * reduces [fill | its right-hand side] to one (m2 + 1) x (m2 + 1) triangle in rows m2 .. 2 m2 + 1 of a (3 m2 + 1) x (m2 + 1) stack,
+ * and this call writes the rows around it. */
 qrk_status qrk_dense_lm_stack(qrk_handle h, const double* qr, int64_t lda, int32_t m2, const double* y2,
                               const double* diag2, const int32_t* perm2, double par, int64_t m1, double* g, int64_t ldg);
 
@@ -429,6 +432,33 @@ typedef struct qrk_lmpar_state {
 } qrk_lmpar_state;
 int qrk_lmpar_begin(qrk_lmpar_state* state, double delta, double par0, double s0, double s1, double s2, double gnorm2);
 int qrk_lmpar_next(qrk_lmpar_state* state, double s0, double s1);
+
+/* ------------------------------------ the R factor of a tall-skinny matrix without Q */
+
+/* r <- an upper triangle R with R^T R = A^T A, by Householder reflectors that are never stored (a tree of QR factorisations: the
+ * condition number is A's, not its square).  The block-angular damped solve reduces the fill [F | f] of qrk_bd_lm_panel with it.
+ *   A    : rows x cols, column-major, leading dimension lda >= rows; rows rows .. lda of a column are never read.  rows >= 0; with
+ *          fewer rows than columns the missing rows count as zero.
+ *   r    : cols x cols, column-major, leading dimension ldr >= cols; exact +0.0 below the diagonal; rows cols .. ldr of a column
+ *          are not touched.  The sign of R's diagonal is not specified.  A column whose remaining part is exactly zero (or has
+ *          a squared norm below DBL_MIN) gets the identity reflector and keeps its diagonal entry, zero if nothing was there: never a NaN; an all-zero A, or rows = 0, gives R = +0.0 everywhere.
+ *   work : qrk_dense_qless_r_work(rows, cols) doubles of the caller's (at least 1): the triangles of level 1 (level_rows[1] * cols
+ *          doubles) followed by those of level 2 (level_rows[2] * cols).
+ * 1 <= cols <= 32; cols = 0 writes nothing; cols > 32 is QRK_STATUS_UNSUPPORTED.  A NULL handle or buffer, a negative size,
+ * lda < rows or ldr < cols is QRK_STATUS_INVALID_ARGUMENT before a device is touched.  DEVICE pointers, enqueue-only on the handle's
+ * stream, no allocation, no synchronisation: the call can be captured.  No atomics; the grid, the chunks and the order of every
+ * operation are a function of (rows, cols) alone, not of the device: two identical calls give identical bits.
+ *
+ * qrk_dense_qless_r_levels reports the schedule: level l reads level_rows[l] rows in chunks of level_chunk[l] rows (a positive
+ * multiple of 256), one workgroup per chunk, each leaving one triangle of cols rows; the triangles of a level are the next level's
+ * rows; the last level has one chunk and writes r.  It returns the number of levels (at most 3; 0 for cols = 0; -1 for a negative
+ * size, cols > 32 or cap < 0) and writes the first min(levels, cap) entries of each array (either may be NULL).  No device is touched.
+ * qrk_dense_qless_r_kernel_name: the kernel of these sizes, or a string that contains "unsupported" ("" for a negative size). */
+int64_t     qrk_dense_qless_r_work(int64_t rows, int32_t cols);
+qrk_status  qrk_dense_qless_r(qrk_handle h, const double* A, int64_t lda, int64_t rows, int32_t cols,
+                              double* r, int64_t ldr, double* work);
+int32_t     qrk_dense_qless_r_levels(int64_t rows, int32_t cols, int64_t* level_rows, int64_t* level_chunk, int32_t cap);
+const char* qrk_dense_qless_r_kernel_name(int64_t rows, int32_t cols);
 
 /* --------------------------------------------- dense right-block solver (angular) */
 

@@ -37,6 +37,7 @@ EXPORTS = (
     "qrk_bd_lm_panel", "qrk_bd_lm_panel_kernel_name", "qrk_dense_lm_stack",
     "qrk_bd_solve_rt", "qrk_bd_solve_rt_kernel_name", "qrk_dense_gemv_t_work", "qrk_dense_gemv_t", "qrk_dense_solve_rt",
     "qrk_dense_trmv_t", "qrk_lmpar_begin", "qrk_lmpar_next",
+    "qrk_dense_qless_r_work", "qrk_dense_qless_r", "qrk_dense_qless_r_levels", "qrk_dense_qless_r_kernel_name",
 )
 
 
@@ -155,6 +156,14 @@ def lib() -> C.CDLL:
     L.qrk_lmpar_begin.argtypes = [C.POINTER(LmparState), C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]
     L.qrk_lmpar_next.restype = C.c_int
     L.qrk_lmpar_next.argtypes = [C.POINTER(LmparState), C.c_double, C.c_double]
+    L.qrk_dense_qless_r_work.restype = C.c_int64
+    L.qrk_dense_qless_r_work.argtypes = [C.c_int64, C.c_int32]
+    L.qrk_dense_qless_r.restype = C.c_int
+    L.qrk_dense_qless_r.argtypes = [vp, dp, C.c_int64, C.c_int64, C.c_int32, dp, C.c_int64, dp]
+    L.qrk_dense_qless_r_levels.restype = C.c_int32
+    L.qrk_dense_qless_r_levels.argtypes = [C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32]
+    L.qrk_dense_qless_r_kernel_name.restype = C.c_char_p
+    L.qrk_dense_qless_r_kernel_name.argtypes = [C.c_int64, C.c_int32]
     L.qrk_dense_plan_create.restype = C.c_int
     L.qrk_dense_plan_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int, C.POINTER(vp)]
     L.qrk_dense_plan_destroy.restype = C.c_int

@@ -199,6 +199,43 @@ class DenseTSQR:
             pass
 
 
+class DenseQlessR:
+    """The R factor of a tall-skinny dense device matrix without Q (qrk_dense_qless_r): R^T R = A^T A by a tree of
+    Householder factorisations whose reflectors are never stored.  A is only read.  At most 32 columns; deterministic; nothing is
+    allocated between calls of one shape, and the call enqueues only (it can be captured once the workspace exists)."""
+
+    def __init__(self, context: Context):
+        self._ctx = context
+        self._shape = None
+        self._r = self._work = None
+
+    def compute(self, A: torch.Tensor):
+        """A: (rows, cols) float64 device tensor in COLUMN-major storage (A.t() contiguous) or a window of one, cols <= 32; any
+        rows >= 0 (missing rows count as zero)."""
+        rows, cols = A.shape
+        assert A.dtype == torch.float64
+        lda = _ld(A)
+        if self._shape != (rows, cols):
+            dev = A.device
+            self._work = torch.empty(int(capi.lib().qrk_dense_qless_r_work(rows, cols)), dtype=torch.float64, device=dev)
+            self._r = torch.zeros(cols, max(cols, 1), dtype=torch.float64, device=dev).t()      # column-major cols x cols
+            self._shape = (rows, cols)
+        self._ctx.use_current_stream()
+        capi.check(capi.lib().qrk_dense_qless_r(self._ctx.handle, A.data_ptr(), lda, rows, cols, self._r.data_ptr(), max(cols, 1),
+                                                self._work.data_ptr()), self._ctx.handle)
+        return self
+
+    def rows(self):
+        return self._shape[0]
+
+    def cols(self):
+        return self._shape[1]
+
+    def matrixR(self) -> torch.Tensor:
+        """Upper-triangular cols x cols (dense, device; exact zeros below the diagonal; the sign of the diagonal is not specified)."""
+        return self._r.clone()
+
+
 class BlockedThinDenseQR(DenseColPivQR):
     """QRKit::BlockedThinDenseQR (BlockedThinDenseQR.h:53-176): Householder QR of a thin dense matrix without column
     pivoting, Q implicit, identity permutations (:139-142).  The reference walks panels of SuggestedBlockCols columns
@@ -436,7 +473,10 @@ class BlockAngularSparseQR:
         self._W = self._Win = None   # rows x (m2 + 1) work matrices of factorizeAndSolve(), kept between calls of one shape
         self._lm_ready = False       # factorizeAndSolve() took the fused route: W holds the factors lmSolve() works on
         self._lm_np = True           # ... and b was a numpy array
-        self._lm = None              # work arrays and dense plan of lmSolve(), kept between calls of one shape
+        self._lm = None              # work arrays and dense plan of lmSolve() on the route in use, kept between calls of one shape
+        self._lm_base = None         # ... the arrays both routes share, and the per-route sets
+        self._lm_routes = {}
+        self._lm_route = "auto"      # setLmRoute()
 
     def compute(self, mat: BlockMatrix1x2):
         self.analyzePattern(mat)
@@ -531,9 +571,15 @@ class BlockAngularSparseQR:
         goes over its last column, and the back substitution is factorizeAndSolve()'s with the damped factors.  The work
         arrays and the dense plan are kept between calls of one shape.
 
+        On the reduced route (lmRoute(); the default for m2 <= 31) the fill goes to a buffer of its own,
+        qrk_dense_qless_r reduces [fill | its right-hand side] (m1 x (m2 + 1)) to one triangle T = [T11 t; 0 rho], and the stack is
+        G2 = [R2 y2; T; sqrt(par) D2(P2) 0], (3 m2 + 1) x (m2 + 1): the same minimiser (rho^2 is a constant of the residual), a
+        dense factorisation that no longer depends on m1, and no zero rows at par = 0.
+
         Returns x in J's column order, numpy or tensor as `b` was given to factorizeAndSolve(); with returnDxNorm2 also
-        || D x ||^2 (a float, from the returned x).  The dense factorisation of G synchronises the stream when
-        (m1 + 2 m2) * m2 >= 2^18 (qrk_dense_factorize): the call cannot be captured into a graph at those sizes.
+        || D x ||^2 (a float, from the returned x).  On the stacked route the dense factorisation of G synchronises the stream when
+        (m1 + 2 m2) * m2 >= 2^18 (qrk_dense_factorize): the call cannot be captured into a graph at those sizes.  The reduced
+        stack has at most 94 x 31 entries and never gets there.
         Raises before a factorizeAndSolve() / computeAndSolve() that took the fused route (rows - m1 >= m2)."""
         self._lm_require("lmSolve()")
         par = float(par)
@@ -546,6 +592,23 @@ class BlockAngularSparseQR:
             dx2 = float(torch.sum((x * d) ** 2 if d is not None else x ** 2).item())
         xo = x.cpu().numpy() if self._lm_np else x
         return (xo, dx2) if returnDxNorm2 else xo
+
+    LM_REDUCED_MAX_COLS = 32         # qrk_dense_qless_r's column limit: the reduced route needs m2 + 1 <= 32
+
+    def setLmRoute(self, route: str):
+        """How lmSolve() / lmpar() finish the right part: "stacked" factorises the (m1 + 2 m2) x m2 stack with the fill in it (K11),
+        "reduced" first reduces the fill to one triangle (K13: needs m2 + 1 <= 32, raises at the next evaluation otherwise),
+        "auto" (the default) takes the reduced route where it can.  Both give the same minimiser; each route repeats its own bits."""
+        if route not in ("auto", "reduced", "stacked"):
+            raise ValueError('setLmRoute(): expected "auto", "reduced" or "stacked"')
+        self._lm_route = route
+
+    def lmRoute(self) -> str:
+        """The route the next evaluation takes: "reduced" or "stacked".  Under "auto" it depends on m2, so it needs the kept factors."""
+        if self._lm_route != "auto":
+            return self._lm_route
+        self._lm_require("lmRoute()")
+        return "reduced" if 1 <= self._m2 < self.LM_REDUCED_MAX_COLS else "stacked"
 
     def _lm_require(self, who: str):
         if not (self.m_isInitialized and self._qless and self._lm_ready):
@@ -562,20 +625,34 @@ class BlockAngularSparseQR:
         return d
 
     def _lm_arrays(self):
-        """The work arrays and the dense plan of the damped evaluation, kept between calls of one shape."""
+        """The work arrays and the dense plan of the damped evaluation on the route in use, kept between calls of one shape.  top, s
+        and colidx are shared by the two routes; the stack G (and the reduced route's fill F and workspace) are the route's own, so
+        the big G exists only once the stacked route has run."""
         dev = self._ctx.device
         m1, m2, left = self._m1, self._m2, self.m_leftSolver
-        ldg = m1 + 2 * m2
-        lm = self._lm
-        if lm is None or lm["key"] != (m1, m2, left._nnz_r):
-            lm = self._lm = {
-                "key": (m1, m2, left._nnz_r),
+        route = self.lmRoute()
+        key = (m1, m2, left._nnz_r)
+        if self._lm_base is None or self._lm_base["key"] != key:
+            self._lm_base = {
+                "key": key,
                 "top": torch.empty(m2 + 1, max(m1, 1), dtype=torch.float64, device=dev).t(),      # column-major m1 x (m2 + 1)
-                "G": torch.empty(m2 + 1, ldg, dtype=torch.float64, device=dev).t(),              # column-major ldg x (m2 + 1)
                 "s": torch.empty(max(left._nnz_r, 1), dtype=torch.float64, device=dev),
-                "dense": DenseColPivQR(self._ctx, capi.HOUSEHOLDER),
                 "colidx": torch.empty(m2 + 1, dtype=torch.int32, device=dev),
             }
+            self._lm_routes = {}
+        lm = self._lm_routes.get(route)
+        if lm is None:
+            lm = self._lm_routes[route] = dict(self._lm_base)
+            lm["route"] = route
+            lm["dense"] = DenseColPivQR(self._ctx, capi.HOUSEHOLDER)
+            if route == "reduced":
+                ldg = 3 * m2 + 1
+                lm["F"] = torch.empty(m2 + 1, max(m1, 1), dtype=torch.float64, device=dev).t()    # column-major m1 x (m2 + 1)
+                lm["qwork"] = torch.empty(int(capi.lib().qrk_dense_qless_r_work(m1, m2 + 1)), dtype=torch.float64, device=dev)
+            else:
+                ldg = m1 + 2 * m2
+            lm["G"] = torch.empty(m2 + 1, ldg, dtype=torch.float64, device=dev).t()              # column-major ldg x (m2 + 1)
+        self._lm = lm
         return lm
 
     def _lm_transposed_arrays(self):
@@ -591,7 +668,8 @@ class BlockAngularSparseQR:
         return lm
 
     def _lm_evaluate(self, d, par: float, transposed: bool):
-        """One damped evaluation on the kept factors: lmSolve()'s chain, and with `transposed` the forward substitution with the
+        """One damped evaluation on the kept factors: lmSolve()'s chain (on the route lmRoute() names: the stack G is the reduced
+        G2 or the stacked G, everything after it is the same), and with `transposed` the forward substitution with the
         damped factor S^ = [S1 Top; 0 Rg] behind it: u = D~^2 z in pivoted order, w1 = S1^-T u1 (qrk_bd_solve_rt
         on s_vals), w2 = Rg^-T (u2 - Top^T w1) (qrk_dense_gemv_t on top, qrk_dense_solve_rt on G's upper triangle).  d: the device
         diag or None.  Returns (x, None), x on the device in J's column order, or (x, (s0, s1, zeros)) with s0 = || D x ||^2,
@@ -599,7 +677,11 @@ class BlockAngularSparseQR:
         dev = self._ctx.device
         m1, m2, rows, W = self._m1, self._m2, self._rows, self._W
         left = self.m_leftSolver
-        ldg = m1 + 2 * m2
+        reduced = self.lmRoute() == "reduced"
+        if reduced and not 1 <= m2 < self.LM_REDUCED_MAX_COLS:
+            raise RuntimeError(f"the reduced LM route needs 1 <= m2 <= {self.LM_REDUCED_MAX_COLS - 1} (m2 = {m2}); "
+                               'setLmRoute("auto") or "stacked"')
+        ldg = 3 * m2 + 1 if reduced else m1 + 2 * m2
         lm = self._lm_transposed_arrays() if transposed else self._lm_arrays()
         top, G, s_vals, colidx = lm["top"], lm["G"], lm["s"], lm["colidx"]
         p2 = self.m_rightSolver.colsPermutation()
@@ -607,11 +689,20 @@ class BlockAngularSparseQR:
         colidx[m2] = m2
         L, h = capi.lib(), self._ctx.handle
         self._ctx.use_current_stream()
-        capi.check(L.qrk_bd_lm_panel(left._plan, left._r.data_ptr(), left._perm.data_ptr(), d.data_ptr() if d is not None else None,
-                                     par, W.data_ptr(), rows, m2 + 1, colidx.data_ptr(), s_vals.data_ptr(), top.data_ptr(), max(m1, 1),
-                                     G.data_ptr() + 8 * m2, ldg), h)
+        if reduced:
+            # the fill to F, [F | f] to the triangle T in rows m2 .. 2 m2 + 1 of G2; the stack kernel sees a "fill" of m2 + 1 rows
+            F = lm["F"]
+            capi.check(L.qrk_bd_lm_panel(left._plan, left._r.data_ptr(), left._perm.data_ptr(), d.data_ptr() if d is not None else None,
+                                         par, W.data_ptr(), rows, m2 + 1, colidx.data_ptr(), s_vals.data_ptr(), top.data_ptr(), max(m1, 1),
+                                         F.data_ptr(), max(m1, 1)), h)
+            capi.check(L.qrk_dense_qless_r(h, F.data_ptr(), max(m1, 1), m1, m2 + 1, G.data_ptr() + 8 * m2, ldg, lm["qwork"].data_ptr()), h)
+        else:
+            capi.check(L.qrk_bd_lm_panel(left._plan, left._r.data_ptr(), left._perm.data_ptr(), d.data_ptr() if d is not None else None,
+                                         par, W.data_ptr(), rows, m2 + 1, colidx.data_ptr(), s_vals.data_ptr(), top.data_ptr(), max(m1, 1),
+                                         G.data_ptr() + 8 * m2, ldg), h)
         capi.check(L.qrk_dense_lm_stack(h, W.data_ptr() + 8 * m1, rows, m2, W.data_ptr() + 8 * (m2 * rows + m1),
-                                        d[m1:].data_ptr() if d is not None else None, p2.data_ptr(), par, m1, G.data_ptr(), ldg), h)
+                                        d[m1:].data_ptr() if d is not None else None, p2.data_ptr(), par, m2 + 1 if reduced else m1,
+                                        G.data_ptr(), ldg), h)
         dense = lm["dense"].compute(G[:, :m2])
         dense.applyQ(G[:, m2:], transpose=True)
         z2 = dense.solveR(G[:m2, m2].clone().reshape(m2, 1))

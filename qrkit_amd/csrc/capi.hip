@@ -1624,6 +1624,40 @@ qrk_status qrk_dense_trmv_t(qrk_handle h, const double* qr, int64_t lda, int32_t
     return QRK_STATUS_OK;
 }
 
+// ---- the R factor of a tall-skinny matrix without Q (dense_qless_r.hip)
+int64_t qrk_dense_qless_r_work(int64_t rows, int32_t cols) { return qrk::dense_qless_r_work(rows, cols); }
+
+int32_t qrk_dense_qless_r_levels(int64_t rows, int32_t cols, int64_t* level_rows, int64_t* level_chunk, int32_t cap)
+{
+    if (rows < 0 || cols < 0 || cols > 32 || cap < 0) return -1;
+    return qrk::qless_r_schedule(rows, cols, level_rows, level_chunk, cap);
+}
+
+const char* qrk_dense_qless_r_kernel_name(int64_t rows, int32_t cols)
+{
+    if (rows < 0 || cols < 0) return "";
+    if (cols == 0) return "none: nothing to do";
+    switch (qrk::dense_qless_r_cap(cols)) {
+    case 8: return "qrk::qless::dense_qless_r_kernel<8>";
+    case 16: return "qrk::qless::dense_qless_r_kernel<16>";
+    case 32: return "qrk::qless::dense_qless_r_kernel<32>";
+    default: return "unsupported: more than 32 columns";
+    }
+}
+
+qrk_status qrk_dense_qless_r(qrk_handle h, const double* A, int64_t lda, int64_t rows, int32_t cols, double* r, int64_t ldr, double* work)
+{
+    if (!h || rows < 0 || cols < 0 || lda < rows)
+        return fail(h, QRK_STATUS_INVALID_ARGUMENT, "qrk_dense_qless_r: bad argument (NULL handle, negative size or lda < rows)");
+    if (cols == 0) return QRK_STATUS_OK;
+    if (cols > 32) return fail(h, QRK_STATUS_UNSUPPORTED, "qrk_dense_qless_r: more than 32 columns");
+    if (!r || !work || ldr < cols || (rows > 0 && !A))
+        return fail(h, QRK_STATUS_INVALID_ARGUMENT, "qrk_dense_qless_r: bad argument (NULL buffer or ldr < cols)");
+    QRK_HIP(h, hipSetDevice(h->device));
+    QRK_HIP(h, qrk::launch_dense_qless_r(A, lda, rows, cols, r, ldr, work, h->stream));
+    return QRK_STATUS_OK;
+}
+
 // The scalar rule of lmpar as a host state machine: qrk_bd_lmpar's steps 1-5, operation for operation (no a * b + c in it, and the
 // pragma keeps it so)
 int qrk_lmpar_begin(qrk_lmpar_state* st, double delta, double par0, double s0, double s1, double s2, double gnorm2)

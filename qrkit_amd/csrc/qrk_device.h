@@ -297,6 +297,13 @@ hipError_t launch_dense_gemv_t(const double* A, int64_t lda, int64_t rows, int64
 hipError_t launch_dense_solve_rt(const double* qr, int64_t lda, int n, double* b, hipStream_t stream);
 hipError_t launch_dense_trmv_t(const double* qr, int64_t lda, int n, const double* y, double* out, hipStream_t stream);
 
+// dense_qless_r.hip: the R factor of a tall-skinny matrix without Q, level by level
+int qless_r_schedule(int64_t rows, int cols, int64_t* level_rows, int64_t* level_chunk, int cap);   // host integer logic; returns the levels
+int64_t dense_qless_r_work(int64_t rows, int cols);
+int dense_qless_r_cap(int cols);          // 8 / 16 / 32 columns of capacity; -1: not supported
+hipError_t launch_dense_qless_r(const double* A, int64_t lda, int64_t rows, int cols, double* r, int64_t ldr, double* work,
+                                hipStream_t stream);
+
 // ---- decision margins of the fast kernels ------------------------------------------------
 // A fast kernel (FMA chains, squared column norms, un-normalised reflector) takes a data-dependent decision of the reference
 // algorithm only when it is clear of rounding, and otherwise sends the tile to the exact path (bdqr_exact.hip), which repeats

@@ -49,6 +49,8 @@ def kept_solvers(qrkit_amd, B, r, c, m2):
         t = torch.randn(B, c, r, generator=g, **f64)                                  # column-major r x c tiles
         J2 = torch.randn(m2 + 1, rows, generator=g, **f64).t()                         # [J2 | b], column-major
         solver = qrkit_amd.BlockAngularSparseQR()
+        if hasattr(solver, "setLmRoute"):          # (the parent build of --parent-root may be older than the routes)
+            solver.setLmRoute("stacked")           # K12's chain, the one the committed table measures (tools/bench_angular_lm_reduced.py: K13's)
         solver.computeAndSolve(qrkit_amd.BlockMatrix1x2(qrkit_amd.SparseBlockDiagonal.fromTiles(brows, bcols, t.reshape(-1)), J2[:, :m2]),
                                J2[:, m2].contiguous())
         kept.append(solver)
